@@ -26,7 +26,14 @@ With N ranks a step covers N repeats (weak scaling: one repeat's rows and one fi
   graph_prediction_c3, communities_c2, graph_queries, explainer_api   (N = 1 only; at N > 1
                   they are listed in the line's `sections_skipped`)
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--sections a,b] [--no-cpu-baseline]
+A plain run (`python bench.py --gpus N --steps K --warmup W`) sets up, warms up, times the K
+steps of the headline and prints the result line.  `--full` adds everything else: the headline's
+phase breakdown (eager steps), its graph / exchange checks against an eager step, its roofline
+and CPU baseline, and the `regimes` sections (`--sections` picks among them).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py --full [--gpus N] [--steps K] [--warmup W] [--sections a,b] [--no-cpu-baseline]
     torchrun --nproc-per-node N bench.py --gpus N ...
 """
 import argparse
@@ -65,9 +72,18 @@ def parse():
     p.add_argument("--query", type=int, default=7)
     p.add_argument("--repeats", type=int, default=1,
                    help="repeats per rank per step (Explainer.run(times=...) / world)")
+    p.add_argument("--full", action="store_true",
+                   help="beside the timed headline steps: its phase breakdown, graph / exchange "
+                        "checks, roofline and CPU baseline, and the regime sections (--sections)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last timed step's outputs (mean / std "
+                        "of the fitted weights; the last fit's weights, logits and kernel weights "
+                        "where the launch form keeps them) as DIR/<name>.npy")
     p.add_argument("--sections", default="all",
-                   help="comma list of " + ",".join(SECTIONS) + " (PMC passes run one each)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+                   help="with --full: comma list of " + ",".join(SECTIONS) +
+                        " (PMC passes run one each)")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="with --full: leave the CPU baselines out")
     p.add_argument("--no-graph", action="store_true",
                    help="headline at world 1: eager launches instead of replaying one captured "
                         "HIP graph per step")
@@ -80,7 +96,10 @@ def parse():
     p.add_argument("--c5-samples", type=int, default=1024)
     p.add_argument("--c4-times", type=int, default=4,
                    help="c4 repeats per job (the job is sharded over the ranks)")
-    return p.parse_args()
+    args = p.parse_args()
+    if not args.full and args.sections not in ("all", "headline"):
+        p.error("--sections other than headline needs --full")
+    return args
 
 
 # ----------------------------------------------------------------------------- plumbing
@@ -180,6 +199,24 @@ def log(rank, msg):
     """Progress on stderr (rank 0): the JSON line stays the only stdout output."""
     if rank == 0:
         print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs: the files' data together stay within this
+
+
+def dump_outputs(out_dir, tensors):
+    """--dump-outputs: each tensor as out_dir/<name>.npy (fp32 as float32, everything else as
+    float64).  An array over its share of DUMP_BYTES is written as a fixed sample: the elements
+    at sorted flat indices drawn once from numpy's default_rng(0)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(tensors))
+    for name, t in tensors.items():
+        a = t.detach().cpu().numpy()
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def host_info():
@@ -390,8 +427,10 @@ def headline(args, dev, world, rank, workload="c2"):
                      "mean / std after its Adam steps on the side stream; prologue untimed; every "
                      "step is one repeat of its own rows, masks and fit; "
                      f"{a2.steps} group(s) = {args.steps} steps timed (device-resident sampler "
-                     "seed advanced inside the graph); phases_ms from eager steps of one group")
-    line["phases_ms_per"] = f"group of {group} repeats"
+                     "seed advanced inside the graph)" +
+                     ("; phases_ms from eager steps of one group" if args.full else ""))
+    if args.full:
+        line["phases_ms_per"] = f"group of {group} repeats"
     return line
 
 
@@ -507,9 +546,9 @@ def _headline_core(args, dev, world, rank, workload="c2", lanes_ok=True):
         step(i, False)
     results = []
     if use_graph:
-        # the phase breakdown comes from 3 eager steps outside the timed region (events cannot
-        # split a graph replay); then one eager dev-seed step and the capture
-        for i in range(3):
+        # --full: the phase breakdown comes from 3 eager steps outside the timed region (events
+        # cannot split a graph replay); then one eager dev-seed step and the capture
+        for i in range(3 if args.full else 0):
             step(args.warmup + i, True)
         step(0, False, dev_seed=True)
         seed_t.fill_(1000 + args.warmup)
@@ -675,17 +714,29 @@ def _headline_core(args, dev, world, rank, workload="c2", lanes_ok=True):
             elif use_graph:
                 results.append(split_step())
             else:
-                step(args.warmup + i, True)
+                eager_out = step(args.warmup + i, True)
     torch.cuda.synchronize()
     barrier(world)
     elapsed = max_over_ranks(time.perf_counter() - t0, world, dev)
     graph_check = exchange_check = None
-    if use_graph:  # outside the timed region: the last step == an eager step on the same seed
-        if pipe:
-            # the last step (index K - 1) is the last lane's last step
-            last = results[-1] if ex else lanes[-1]["graphs"][(per_lane // unroll - 1) & 1][1][-1]
-        else:
-            last = results[-1] if split else g_out
+    # the last timed step's result: (mean, std) of the fitted weights over the step's repeats
+    if not use_graph:
+        last = eager_out
+    elif pipe:
+        # the last step (index K - 1) is the last lane's last step
+        last = results[-1] if ex else lanes[-1]["graphs"][(per_lane // unroll - 1) & 1][1][-1]
+    else:
+        last = results[-1] if split else g_out
+    if args.dump_outputs and rank == 0:
+        arrays = {"weights_mean": last[0], "weights_std": last[1]}
+        if pipe:  # the buffer set of this rank's last fit (the other set holds the next repeat)
+            d = lanes[-1]["sets"][(per_lane - 1) & 1]
+            arrays.update(fit_weights=d["fit"].w, logits=d["y"][:, 0], kernel_weights=d["k"])
+        elif use_graph:  # the static buffers of the last replay
+            arrays.update(fit_weights=stash["w"], logits=stash["y"], kernel_weights=stash["k"])
+        dump_outputs(args.dump_outputs, arrays)
+    if use_graph and args.full:
+        # outside the timed region: the last step == an eager step on the same seed
         ref = step(args.warmup + args.steps - 1, False)
         graph_check = max(float((last[0] - ref[0]).abs().max()), float((last[1] - ref[1]).abs().max()))
         if pipe and ex:
@@ -708,7 +759,8 @@ def _headline_core(args, dev, world, rank, workload="c2", lanes_ok=True):
                           f"nan {int(torch.isnan(g.double()).sum())} shape {tuple(g.shape)} vs {tuple(e.shape)}")
     for st in statuses:  # outside the timed region: every fit's (sticky) exchange status
         engine.check_fit_status(st)
-    phase_ms = {k: float(np.mean([a.elapsed_time(b) for a, b in v])) for k, v in ev.items()}
+    phase_ms = {k: float(np.mean([a.elapsed_time(b) for a, b in v])) for k, v in ev.items()} \
+        if ev["wlm"] else None  # (a plain run of the captured graphs records no eager phases)
     total_rows = n_rows * args.steps
     wl = wlm_bytes(R, S, batch) * (f1 - f0)
     line = {
@@ -761,17 +813,24 @@ def _headline_core(args, dev, world, rank, workload="c2", lanes_ok=True):
                               "prologue untimed, K fits + K productions timed; every step is "
                               "one repeat of its own rows, masks and fit)"
                               if pipe else "one captured HIP graph replayed per step") +
-                              " (device-resident sampler seed advanced inside the graph); "
-                              "phases_ms from eager steps")},
+                              " (device-resident sampler seed advanced inside the graph)" +
+                              ("; phases_ms from eager steps" if args.full else ""))},
+        "fit_status": "clean (sticky status words of every fit checked after the timed region)",
+    }
+    if args.dump_outputs:
+        line["outputs_dumped"] = args.dump_outputs
+    if not args.full:  # a plain run: the timed steps alone
+        del plan
+        return line
+    line.update({
         "phases_ms": phase_ms,
         "graph_check_max_abs_diff": graph_check,
         "exchange_check_max_abs_diff": exchange_check,
-        "fit_status": "clean (sticky status words of every fit checked after the timed region)",
         "roofline": dict(roofline(wl, phase_ms["wlm"] * 1e-3, "headline", WLM_KERNELS),
                          kernel="surrogate fit chain (" + ", ".join(WLM_KERNELS) + ")",
                          note="latency-bound (51 sequential Adam steps, SURVEY.md §8d regime "
                               "(i)); the HBM fraction is reported, not the bound"),
-    }
+    })
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline_subgraph(args, arch, wdef["kind"], sub_feat, sub_ei,
                                                      q, n_samples)
@@ -1571,6 +1630,7 @@ def node_c3_section(args, dev, world, rank):
     """configs[2] in node_prediction semantics (regime (i)): the headline's repeat pipeline on the
     c3 graph's computational subgraph of node 7 (SAGE 128, interpret_samples=512), one repeat
     per rank per step (weak scaling), with its own graph check and CPU baseline."""
+    args = argparse.Namespace(**dict(vars(args), dump_outputs=None))  # (the headline's dump stays)
     line = headline(args, dev, world, rank, workload="c3node")
     keep = ("value", "ms_per_step", "graph_check_max_abs_diff", "exchange_check_max_abs_diff",
             "phases_ms", "cpu_baseline", "scaling")
@@ -1758,7 +1818,10 @@ def main():
     from bikg_graph_explainability_public_amd import _lib
     _lib.load()
     layout = rank_layout(world, local)
-    want = SECTIONS if args.sections == "all" else tuple(args.sections.split(","))
+    if not args.full:  # a plain run: the headline's timed steps and nothing else
+        want = ("headline",)
+    else:
+        want = SECTIONS if args.sections == "all" else tuple(args.sections.split(","))
     skipped = ()
     if world > 1:
         skipped = tuple(s for s in want if s not in MULTI_GPU_SECTIONS)

@@ -27,8 +27,10 @@ def _bench(gpus, sections, extra_env=None, timeout=110, extra_args=()):
     env = dict(os.environ)
     env.update(extra_env or {})
     env["PYTHONUNBUFFERED"] = "1"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--sections",
-           sections, "--steps", "4", "--warmup", "1", "--no-cpu-baseline"] + list(extra_args)
+    # --full: the sections and the headline's graph / exchange checks are behind it
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(gpus),
+           "--sections", sections, "--steps", "4", "--warmup", "1", "--no-cpu-baseline"] + \
+        list(extra_args)
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     assert out.returncode == 0, out.stderr[-4000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
