@@ -11,11 +11,11 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libxpgnn.so")
-ABI_VERSION = 21
+ABI_VERSION = 22
 MAX_TERMS = 8
 
 ACT = {None: 0, "identity": 0, "relu": 1, "sigmoid": 2, "tanh": 3, "leaky_relu": 4, "elu": 5}
-TERM = {"gcn": 0, "mean": 1, "root": 2}
+TERM = {"gcn": 0, "mean": 1, "root": 2, "att": 3}
 
 c_i32, c_i64, c_f32, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -30,7 +30,9 @@ class FitExchangeError(RuntimeError):
 
 
 class TermDesc(ctypes.Structure):
-    _fields_ = [("kind", c_i32), ("rel", c_i32), ("table", c_vp), ("dst_type", c_i32)]
+    _fields_ = [("kind", c_i32), ("rel", c_i32), ("table", c_vp), ("dst_type", c_i32),
+                ("heads", c_i32), ("head_ch", c_i32), ("neg_slope", c_f32), ("self_loops", c_i32),
+                ("att_src", c_vp), ("att_dst", c_vp)]
 
 
 class LayerDesc(ctypes.Structure):

@@ -1023,6 +1023,202 @@ __global__ __launch_bounds__(256) void k_agg(AggArgs a) {
   }
 }
 
+// ------------------------------------------------------------------------------------ attention
+// Graph attention (XPG_TERM_ATT, GATConv; the rules are in xpgnn.h).  Layers of ATT terms run on
+// kernels of their own: the per-edge weight depends on the mask row through a softmax over the
+// target's kept in-edges, which k_agg's fixed per-edge coefficients cannot express.
+struct AttArgs {
+  int64_t rows;
+  int n_tgt, n_prev, n_terms;
+  int width;  // source row width (floats, % 32 == 0); lps = width / 4 lanes per item
+  int lps;
+  const int32_t* tgt_prev;
+  const int32_t* tgt_f0;
+  const int32_t* agg_ptr;
+  const int32_t* agg_src;
+  const int32_t* agg_f0;
+  const int32_t* self_mult;
+  const int32_t* tgt_type;
+  const int32_t* f0_node;
+  const uint32_t* bits;
+  int words;
+  int rel[XPG_MAX_TERMS];
+  int dst_type[XPG_MAX_TERMS];
+  int heads[XPG_MAX_TERMS];
+  int head_ch[XPG_MAX_TERMS];
+  int self_loops[XPG_MAX_TERMS];
+  int slice0[XPG_MAX_TERMS];  // layer >= 2: the term's first slice of the GEMM input
+  int slot0[XPG_MAX_TERMS];   // layer >= 2: the term's first score slot (heads src, then heads dst)
+  float neg_slope[XPG_MAX_TERMS];
+  const float* table[XPG_MAX_TERMS];    // layer 1: [n0][width]
+  const float* att_src[XPG_MAX_TERMS];  // layer 1: [n0][heads]; layer >= 2: [heads][width]
+  const float* att_dst[XPG_MAX_TERMS];
+  const float* hprev;  // layer >= 2 source rows [rows][n_prev][width]
+  float* score;        // layer >= 2: [rows][n_prev][n_slots] (k_att_score writes, k_agg_att reads)
+  int n_slots;
+  float* out;
+  int64_t out_ld;
+  const float* bias;  // layer 1 epilogue ([n_types][width] with tgt_type)
+  int act;
+  int f_real;
+};
+
+__device__ __forceinline__ float leaky(float x, float slope) { return x > 0.f ? x : slope * x; }
+
+// Layer >= 2 score pre-pass: score[b][u][slot] = <v_slot, hprev[b][u]> for every (mask row,
+// previous-frontier node) and every slot of the layer (per ATT term its heads' v_s, then its
+// heads' v_d): a source is read by many targets, so its scores are computed once, not per edge.
+__global__ __launch_bounds__(256) void k_att_score(AttArgs a) {
+  const int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (idx >= a.rows * a.n_prev * a.n_slots) return;
+  const int64_t node = idx / a.n_slots;  // (b, u)
+  const int slot = static_cast<int>(idx - node * a.n_slots);
+  int k = 0;
+  while (k + 1 < a.n_terms && slot >= a.slot0[k + 1]) ++k;
+  const int j = slot - a.slot0[k];
+  const float* vec = (j < a.heads[k] ? a.att_src[k] + (int64_t)j * a.width
+                                     : a.att_dst[k] + (int64_t)(j - a.heads[k]) * a.width);
+  const float4* v = reinterpret_cast<const float4*>(vec);
+  const float4* x = reinterpret_cast<const float4*>(a.hprev + node * a.width);
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int c = 0; c < a.width / 4; ++c) {
+    const float4 xv = x[c], vv = v[c];
+    acc.x = fmaf(xv.x, vv.x, acc.x);
+    acc.y = fmaf(xv.y, vv.y, acc.y);
+    acc.z = fmaf(xv.z, vv.z, acc.z);
+    acc.w = fmaf(xv.w, vv.w, acc.w);
+  }
+  a.score[idx] = (acc.x + acc.y) + (acc.z + acc.w);
+}
+
+// Masked attention aggregation of one conv layer.  Item = (mask row b, target t), lps lanes per
+// item, each lane owns one float4 chunk of the row (as k_agg with NV = 1).  Per ATT term and head
+// two passes over the target's CSR range: keep test, logit and running max; then exp, denominator
+// and the weighted sum, normalised by 1 / (den + 1e-16).  A source's keep test is its own mask
+// bit.  L1: sources are the shared tables, a lane visits only the heads its chunk touches (a chunk
+// straddles heads when head_ch % 4 != 0) and keeps the columns of the head at hand; the epilogue
+// is k_agg<true>'s.  Otherwise sources are the previous layer's rows and head h of term k fills
+// slice slice0[k] + h of the GEMM input.
+template <bool L1>
+__global__ __launch_bounds__(256) void k_agg_att(AttArgs a) {
+  const int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t item = gid / a.lps;
+  const int sub = static_cast<int>(gid - item * a.lps);
+  if (item >= a.rows * a.n_tgt) return;
+  const int64_t b = item / a.n_tgt;
+  const int t = static_cast<int>(item - b * a.n_tgt);
+  const uint32_t* mrow = a.bits + b * a.words;
+  const int t0 = a.tgt_f0[t];
+  const int tp = a.tgt_prev[t];
+  const bool t_on = bit_of(mrow, a.f0_node[t0]);
+  const int f0 = sub * 4;
+  float4 tot = make_float4(0.f, 0.f, 0.f, 0.f);
+  constexpr int EB = 4;  // in-edges whose edge -> keep word -> score / row loads are issued together
+
+  for (int k = 0; k < a.n_terms; ++k) {
+    const int H = a.heads[k], C = a.head_ch[k], r = a.rel[k];
+    const float slope = a.neg_slope[k];
+    const bool gated = a.tgt_type && a.dst_type[k] >= 0 && a.tgt_type[t] != a.dst_type[k];
+    const int* pp = a.agg_ptr + (int64_t)r * (a.n_tgt + 1);
+    // non-self in-edges take part only while the target itself is kept
+    const int e0 = pp[t], e1 = t_on ? pp[t + 1] : pp[t];
+    const int n_self = a.self_loops[k] ? 1 : (t_on ? a.self_mult[(int64_t)r * a.n_tgt + t] : 0);
+    const float* base = L1 ? a.table[k] : a.hprev + b * (int64_t)a.n_prev * a.width;
+    const float* sc = L1 ? a.att_src[k] : a.score + b * (int64_t)a.n_prev * a.n_slots + a.slot0[k];
+    const int sc_ld = L1 ? H : a.n_slots;
+    const int self_pos = L1 ? t0 : tp;
+    int h_lo = 0, h_hi = H - 1;
+    if (L1) {
+      h_lo = f0 / C;
+      h_hi = (f0 + 3) / C < H - 1 ? (f0 + 3) / C : H - 1;  // h_lo > h_hi: a lane of padded columns
+    }
+    for (int h = h_lo; h <= h_hi; ++h) {
+      float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (!gated) {
+        const float ad = L1 ? a.att_dst[k][(int64_t)t0 * H + h] : sc[(int64_t)tp * sc_ld + H + h];
+        const float z_self = leaky(sc[(int64_t)self_pos * sc_ld + h] + ad, slope);
+        float m = n_self > 0 ? z_self : -INFINITY;
+        for (int eb = e0; eb < e1; eb += EB) {
+          int up[EB], nd[EB];
+          bool kp[EB];
+          float as[EB];
+#pragma unroll
+          for (int q = 0; q < EB; ++q) {
+            const int e = eb + q < e1 ? eb + q : eb;
+            nd[q] = a.agg_f0[e];
+            up[q] = L1 ? nd[q] : a.agg_src[e];
+          }
+#pragma unroll
+          for (int q = 0; q < EB; ++q) nd[q] = a.f0_node[nd[q]];
+#pragma unroll
+          for (int q = 0; q < EB; ++q) kp[q] = bit_of(mrow, nd[q]) && eb + q < e1;
+#pragma unroll
+          for (int q = 0; q < EB; ++q) as[q] = kp[q] ? sc[(int64_t)up[q] * sc_ld + h] : 0.f;
+#pragma unroll
+          for (int q = 0; q < EB; ++q)
+            if (kp[q]) m = fmaxf(m, leaky(as[q] + ad, slope));
+        }
+        float den = 0.f;
+        if (n_self > 0) {
+          const float p = __expf(z_self - m) * static_cast<float>(n_self);
+          den = p;
+          fma4(s, p, reinterpret_cast<const float4*>(base + (int64_t)self_pos * a.width)[sub]);
+        }
+        for (int eb = e0; eb < e1; eb += EB) {
+          int up[EB], nd[EB];
+          bool kp[EB];
+          float as[EB];
+          float4 v[EB];
+#pragma unroll
+          for (int q = 0; q < EB; ++q) {
+            const int e = eb + q < e1 ? eb + q : eb;
+            nd[q] = a.agg_f0[e];
+            up[q] = L1 ? nd[q] : a.agg_src[e];
+          }
+#pragma unroll
+          for (int q = 0; q < EB; ++q) nd[q] = a.f0_node[nd[q]];
+#pragma unroll
+          for (int q = 0; q < EB; ++q) kp[q] = bit_of(mrow, nd[q]) && eb + q < e1;
+#pragma unroll
+          for (int q = 0; q < EB; ++q) {
+            as[q] = kp[q] ? sc[(int64_t)up[q] * sc_ld + h] : 0.f;
+            v[q] = kp[q] ? reinterpret_cast<const float4*>(base + (int64_t)up[q] * a.width)[sub]
+                         : make_float4(0.f, 0.f, 0.f, 0.f);
+          }
+#pragma unroll
+          for (int q = 0; q < EB; ++q) {
+            if (kp[q]) {
+              const float p = __expf(leaky(as[q] + ad, slope) - m);
+              den += p;
+              fma4(s, p, v[q]);
+            }
+          }
+        }
+        const float inv = 1.f / (den + 1e-16f);
+        s.x *= inv; s.y *= inv; s.z *= inv; s.w *= inv;
+      }
+      if (L1) {
+        // the chunk's columns of head h only (columns past heads * head_ch belong to no head)
+        tot.x += (f0 + 0) / C == h ? s.x : 0.f;
+        tot.y += (f0 + 1) / C == h ? s.y : 0.f;
+        tot.z += (f0 + 2) / C == h ? s.z : 0.f;
+        tot.w += (f0 + 3) / C == h ? s.w : 0.f;
+      } else {
+        float4* o = reinterpret_cast<float4*>(a.out + item * a.out_ld + (int64_t)(a.slice0[k] + h) * a.width);
+        o[sub] = s;
+      }
+    }
+  }
+  if (L1) {
+    float4* o = reinterpret_cast<float4*>(a.out + item * a.out_ld);
+    const float* bias = a.bias + (a.tgt_type ? (int64_t)a.tgt_type[t] * a.width : 0);
+    float v[4] = {tot.x, tot.y, tot.z, tot.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[q] = (f0 + q < a.f_real) ? act_apply(v[q] + bias[f0 + q], a.act) : 0.f;
+    o[sub] = make_float4(v[0], v[1], v[2], v[3]);
+  }
+}
+
 // One term of k_agg_l1_rows for the wave's 64 rows and W features: s (all 0 on entry) gets the
 // term's value, in k_agg<true>'s operation order.  Features are handled in pairs (f32x2: packed
 // fp32 add / fma / mul, two features per VALU instruction; each lane's operations per feature are
@@ -5550,6 +5746,39 @@ bool plan_multi_type(const xpg_forward_plan* p) {
   return false;
 }
 
+// attention (XPG_TERM_ATT) layers run on the multi-kernel path only
+bool layer_has_attention(const xpg_layer_desc& ly) {
+  for (int k = 0; k < ly.n_terms && k < XPG_MAX_TERMS; ++k)
+    if (ly.terms[k].kind == XPG_TERM_ATT) return true;
+  return false;
+}
+bool plan_has_attention(const xpg_forward_plan* p) {
+  for (int l = 0; l < p->n_layers; ++l)
+    if (layer_has_attention(p->layers[l])) return true;
+  return false;
+}
+// an all-attention plan reads no in-degrees: k_degree is not launched for it
+bool plan_needs_degree(const xpg_forward_plan* p) {
+  for (int l = 0; l < p->n_layers; ++l)
+    for (int k = 0; k < p->layers[l].n_terms && k < XPG_MAX_TERMS; ++k)
+      if (p->layers[l].terms[k].kind != XPG_TERM_ATT) return true;
+  return p->edge_masks != 0;
+}
+// GEMM-input slices of a layer >= 2 (one per term; an ATT term has one per head) and its score
+// slots (per ATT term: heads source scores, then heads destination scores)
+int layer_slices(const xpg_layer_desc& ly) {
+  int n = 0;
+  for (int k = 0; k < ly.n_terms && k < XPG_MAX_TERMS; ++k)
+    n += ly.terms[k].kind == XPG_TERM_ATT ? std::max(1, ly.terms[k].heads) : 1;
+  return n;
+}
+int layer_score_slots(const xpg_layer_desc& ly) {
+  int n = 0;
+  for (int k = 0; k < ly.n_terms && k < XPG_MAX_TERMS; ++k)
+    if (ly.terms[k].kind == XPG_TERM_ATT) n += 2 * std::max(1, ly.terms[k].heads);
+  return n;
+}
+
 // k_degree's kept prefix of F_0 (see k_degree): F_1 for plans without GCN terms or edge masks
 int deg_pitch(const xpg_forward_plan* p) {
   if (p->edge_masks) return p->n0;
@@ -5560,7 +5789,7 @@ int deg_pitch(const xpg_forward_plan* p) {
 }
 
 struct WsLayout {
-  size_t kin = 0, agg = 0, head0 = 0, head1 = 0, ctl = 0, total = 0;
+  size_t kin = 0, agg = 0, head0 = 0, head1 = 0, score = 0, ctl = 0, total = 0;
   size_t h[64];
 };
 
@@ -5569,14 +5798,16 @@ int layout_ws(const xpg_forward_plan* p, int64_t rows, WsLayout* L) {
   size_t off = 0;
   L->kin = off;
   off += align_up(sizeof(float) * (size_t)rows * p->n_rel * deg_pitch(p));
-  size_t agg_max = 0;
+  size_t agg_max = 0, score_max = 0;
   for (int l = 0; l < p->n_layers; ++l) {
     const xpg_layer_desc& ly = p->layers[l];
     L->h[l] = off;
     off += align_up(sizeof(float) * (size_t)rows * ly.n_tgt * ly.f_out_pad);
     if (l > 0) {
-      size_t a = sizeof(float) * (size_t)rows * ly.n_tgt * ly.n_terms * ly.f_in_pad;
+      size_t a = sizeof(float) * (size_t)rows * ly.n_tgt * layer_slices(ly) * ly.f_in_pad;
       agg_max = a > agg_max ? a : agg_max;
+      size_t sc = sizeof(float) * (size_t)rows * p->layers[l - 1].n_tgt * layer_score_slots(ly);
+      score_max = sc > score_max ? sc : score_max;
     }
   }
   L->agg = off;
@@ -5591,6 +5822,8 @@ int layout_ws(const xpg_forward_plan* p, int64_t rows, WsLayout* L) {
   off += align_up(hmax);
   L->head1 = off;
   off += align_up(hmax);
+  L->score = off;  // attention layers' score pre-pass (0 bytes for plans without ATT terms)
+  off += align_up(score_max);
   L->ctl = off;  // the rows forward's block-scheduling counters (zeroed before each launch)
   off += align_up(sizeof(int) * 32);
   L->total = off;
@@ -5679,6 +5912,80 @@ int launch_agg(const AggArgs& a, hipStream_t st) {
   return fail(XPG_EINVAL, "agg: unsupported row width " + std::to_string(a.width));
 }
 
+// One attention layer (every term XPG_TERM_ATT): layer 1 writes hout; a deeper layer runs the score
+// pre-pass and fills the layer's GEMM input (the caller's launch_dense follows).
+int launch_att_layer(const xpg_forward_plan* p, int l, const uint32_t* bits, int64_t rows, const float* hprev,
+                     float* score, float* out, hipStream_t st) {
+  const xpg_layer_desc& ly = p->layers[l];
+  XPG_REQ(!p->edge_masks, "attention terms do not take edge-mask plans");
+  XPG_REQ(p->f0_node, "attention terms need f0_node");
+  AttArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.rows = rows;
+  a.n_tgt = ly.n_tgt;
+  a.n_prev = l == 0 ? p->n0 : p->layers[l - 1].n_tgt;
+  a.n_terms = ly.n_terms;
+  a.width = l == 0 ? ly.f_out_pad : ly.f_in_pad;
+  XPG_REQ(a.width % 32 == 0 && a.width > 0 && a.width <= 256, "attention: row width must be 32..256, a multiple of 32");
+  a.lps = a.width / 4;
+  a.tgt_prev = ly.tgt_prev;
+  a.tgt_f0 = ly.tgt_f0;
+  a.agg_ptr = ly.agg_ptr;
+  a.agg_src = ly.agg_src;
+  a.agg_f0 = ly.agg_f0;
+  a.self_mult = ly.self_mult;
+  a.tgt_type = ly.tgt_type;
+  a.f0_node = p->f0_node;
+  a.bits = bits;
+  a.words = words_of(p->cols);
+  int slices = 0, slots = 0;
+  for (int k = 0; k < ly.n_terms; ++k) {
+    const xpg_term_desc& td = ly.terms[k];
+    XPG_REQ(td.kind == XPG_TERM_ATT, "layer: attention terms cannot be mixed with other kinds");
+    XPG_REQ(td.rel >= 0 && td.rel < p->n_rel, "term: bad relation");
+    XPG_REQ(!ly.tgt_type || td.dst_type < ly.n_types, "term: destination type out of range");
+    XPG_REQ(td.heads >= 1 && td.head_ch >= 1 && (int64_t)td.heads * td.head_ch <= ly.f_out_pad,
+            "attention term: heads * head_ch must fit the layer's output width");
+    XPG_REQ(td.att_src && td.att_dst && (l > 0 || td.table), "attention term: missing score vectors or table");
+    a.rel[k] = td.rel;
+    a.dst_type[k] = ly.tgt_type ? td.dst_type : -1;
+    a.heads[k] = td.heads;
+    a.head_ch[k] = td.head_ch;
+    a.self_loops[k] = td.self_loops ? 1 : 0;
+    a.neg_slope[k] = td.neg_slope;
+    a.table[k] = td.table;
+    a.att_src[k] = td.att_src;
+    a.att_dst[k] = td.att_dst;
+    a.slice0[k] = slices;
+    a.slot0[k] = slots;
+    slices += td.heads;
+    slots += 2 * td.heads;
+  }
+  a.n_slots = slots;
+  a.out = out;
+  const int64_t threads = rows * ly.n_tgt * a.lps;
+  if (threads == 0) return XPG_OK;
+  const dim3 grid(static_cast<unsigned>(cdiv(threads, 256))), block(256);
+  if (l == 0) {
+    a.out_ld = ly.f_out_pad;
+    a.bias = ly.bias;
+    a.act = ly.act;
+    a.f_real = ly.f_out;
+    hipLaunchKernelGGL(k_agg_att<true>, grid, block, 0, st, a);
+    XPG_LAUNCHED();
+    return XPG_OK;
+  }
+  a.hprev = hprev;
+  a.score = score;
+  a.out_ld = (int64_t)slices * ly.f_in_pad;
+  const int64_t n_sc = rows * a.n_prev * slots;
+  hipLaunchKernelGGL(k_att_score, dim3(static_cast<unsigned>(cdiv(n_sc, 256))), block, 0, st, a);
+  XPG_LAUNCHED();
+  hipLaunchKernelGGL(k_agg_att<false>, grid, block, 0, st, a);
+  XPG_LAUNCHED();
+  return XPG_OK;
+}
+
 // XPG_FORWARD=rows|fused|unfused|wide forces one xpg_masked_forward path (tests, A/B); unset or
 // empty: the plan picks it
 bool forward_is(const char* v) {
@@ -5690,6 +5997,7 @@ bool forward_is(const char* v) {
 int try_fused_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t rows, float* y, hipStream_t st) {
   // opt-in (XPG_FORWARD=fused): per-row latency chains make it slower than k_rows_forward
   if (!forward_is("fused")) return 1;
+  if (plan_has_attention(p)) return 1;  // attention: multi-kernel path only
   if (p->n_layers > kFusedMaxLayers || p->n_head > kFusedMaxHead || plan_multi_type(p)) return 1;
   if (p->edge_masks || p->edge_dot) return 1;  // edge problems: multi-kernel path only
   FusedArgs a;
@@ -5958,6 +6266,7 @@ int wide_side(WideSide** out) {
 
 bool wide_wanted(const xpg_forward_plan* p) {
   if (p->edge_masks || p->edge_dot) return false;  // edge problems: multi-kernel path only
+  if (plan_has_attention(p)) return false;          // attention: multi-kernel path only
   if (forward_is("wide")) return true;
   if (forward_is(nullptr)) return false;  // another path forced
   return p->n_layers == 2 && p->layers[0].n_tgt >= 8192;
@@ -6195,6 +6504,7 @@ int try_rows_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t ro
                      int* ctl) {
   if (p->n_layers < 1 || p->n_layers > 2 || p->n_head > kFusedMaxHead || plan_multi_type(p)) return 1;
   if (p->edge_masks || p->edge_dot) return 1;  // edge problems: multi-kernel path only
+  if (plan_has_attention(p)) return 1;         // attention: multi-kernel path only
   RowsFwdArgs a;
   std::memset(&a, 0, sizeof(a));
   a.rows = rows;
@@ -6762,7 +7072,7 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
       fh.y = y;
     }
   }
-  {
+  if (plan_needs_degree(p)) {
     const int64_t n = rows * (int64_t)p->n_rel * kpitch;
     XPG_REQ(!p->edge_masks || p->deg_eid || p->n_deg_edges == 0, "masked_forward: edge-mask plan without deg_eid");
     hipLaunchKernelGGL(k_degree, dim3(static_cast<unsigned>(cdiv(n, 256))), dim3(256), 0, st, bits, rows, words, p->n0,
@@ -6772,6 +7082,26 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
   for (int l = 0; l < p->n_layers; ++l) {
     const xpg_layer_desc& ly = p->layers[l];
     XPG_REQ(ly.n_terms >= 1 && ly.n_terms <= XPG_MAX_TERMS, "layer: 1..8 terms");
+    if (layer_has_attention(ly)) {
+      float* hout = reinterpret_cast<float*>(ws + L.h[l]);
+      if (l == 0) {
+        rc = launch_att_layer(p, l, bits, rows, nullptr, nullptr, hout, st);
+        if (rc) return rc;
+        continue;
+      }
+      const xpg_layer_desc& prev = p->layers[l - 1];
+      XPG_REQ(ly.f_in_pad == prev.f_out_pad && ly.weight, "layer: f_in_pad must equal previous f_out_pad");
+      float* agg = reinterpret_cast<float*>(ws + L.agg);
+      rc = launch_att_layer(p, l, bits, rows, reinterpret_cast<const float*>(ws + L.h[l - 1]),
+                            reinterpret_cast<float*>(ws + L.score), agg, st);
+      if (rc) return rc;
+      const int64_t K = (int64_t)layer_slices(ly) * ly.f_in_pad;
+      const bool fuse_here = fuse_out && p->n_head == 1 && l == p->n_layers - 1;
+      rc = launch_dense(agg, rows * ly.n_tgt, K, ly.weight, K, K, ly.bias, ly.f_out, ly.f_out_pad, ly.act, hout,
+                        ly.f_out_pad, st, ly.tgt_type, ly.n_tgt, ly.f_out_pad, fuse_here ? &fh : nullptr);
+      if (rc) return rc;
+      continue;
+    }
     AggArgs a;
     std::memset(&a, 0, sizeof(a));
     a.rows = rows;

@@ -21,6 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import ACT, TERM, ForwardPlanDesc, HeadDesc, LayerDesc, WlmParams, call, ptr
+from .program import fold_attention, stack_attention
 
 
 def _rup(x, m):
@@ -645,6 +646,8 @@ def h2d(a, device):
     return out
 
 
+_ATT_MAX_SLICES = 32  # (relation, head) slices of one attention layer's dense input
+
 # ForwardPlan drops the relation terms of other destination types from a layer whose targets
 # share one node type (they add exactly 0); False keeps every term (the parity suite's reference)
 PLAN_DROP_OTHER_TYPES = True
@@ -726,6 +729,11 @@ class ForwardPlan:
             if f_out_pad > 256 or len(conv.terms) > _lib.MAX_TERMS:
                 raise ValueError("conv wider than 256 or more than 8 terms is not supported")
             terms = list(conv.terms)
+            att = any(t.kind == "att" for t in terms)
+            if att and not all(t.kind == "att" for t in terms):
+                raise ValueError("a conv layer mixing attention with other terms is not supported")
+            if att and self.edge_masks:
+                raise ValueError("attention terms on edge-mask plans are not supported")
             if nt_np is not None:
                 # every target of this layer has one node type: a relation term of another
                 # destination type adds exactly 0 to every target (HeteroConv sums per
@@ -736,6 +744,9 @@ class ForwardPlan:
                     kept = [t for t in terms if t.dst_type < 0 or t.dst_type == int(tt[0])]
                     terms = kept or terms
             self.terms_kept.append(len(terms))
+            if att and li > 0 and sum(t.heads for t in terms) > _ATT_MAX_SLICES:
+                raise ValueError(f"attention layer with more than {_ATT_MAX_SLICES} head slices "
+                                 "is not supported")
             self.lowering.append(tuple((t.kind, t.rel, t.dst_type) for t in terms))
             ld = self._layers[li]
             ld.n_terms = len(terms)
@@ -775,6 +786,10 @@ class ForwardPlan:
                 ld.terms[k].kind = TERM[term.kind]
                 ld.terms[k].rel = term.rel
                 ld.terms[k].dst_type = term.dst_type
+                if term.kind == "att":
+                    ld.terms[k].heads, ld.terms[k].head_ch = term.heads, term.head_ch
+                    ld.terms[k].neg_slope = term.neg_slope
+                    ld.terms[k].self_loops = int(term.self_loops)
             if li == 0:
                 for k, term in enumerate(terms):
                     T = dense(X0, term.weight.to(device), None, None)
@@ -782,7 +797,33 @@ class ForwardPlan:
                     Tp[:, :conv.f_out] = T
                     self._keep.append(Tp)
                     ld.terms[k].table = Tp.data_ptr()
+                    if term.kind == "att":
+                        # per-plan score tables a_s / a_d [n0][heads], shared by every mask row:
+                        # X0 times the attention vectors folded through W_src / W_dst
+                        v_s, v_d = self._program_tensor(
+                            program, ("att_l1", li, id(term)),
+                            lambda term=term: tuple(v.to(device).contiguous()
+                                                    for v in fold_attention(term)))
+                        a_s = dense(X0, v_s, None, None).contiguous()
+                        a_d = dense(X0, v_d, None, None).contiguous()
+                        self._keep += [a_s, a_d]
+                        ld.terms[k].att_src, ld.terms[k].att_dst = a_s.data_ptr(), a_d.data_ptr()
                 ld.weight = None
+            elif att:
+                # one f_in_pad-wide slice of the dense input per (term, head): head h's rows of
+                # W_src in slice (k, h), zeros elsewhere, so the layer stays aggregate-then-transform
+                def make_att(terms=terms, prev_pad=prev_pad, f_out_pad=f_out_pad):
+                    w, vecs = stack_attention(terms, prev_pad, f_out_pad)
+                    return (w.to(device=device, dtype=torch.float32).contiguous(),
+                            [tuple(v.to(device=device, dtype=torch.float32).contiguous() for v in pr)
+                             for pr in vecs])
+                Wc, vecs = self._program_tensor(program, ("wc_att", li, tuple(id(t) for t in terms)),
+                                                make_att)
+                self._keep.append(Wc)
+                ld.weight = Wc.data_ptr()
+                for k, (v_s, v_d) in enumerate(vecs):
+                    self._keep += [v_s, v_d]
+                    ld.terms[k].att_src, ld.terms[k].att_dst = v_s.data_ptr(), v_d.data_ptr()
             else:
                 def make_wc(conv=conv, terms=terms, prev_pad=prev_pad, f_out_pad=f_out_pad):
                     w = torch.zeros((f_out_pad, len(terms) * prev_pad), dtype=torch.float32,

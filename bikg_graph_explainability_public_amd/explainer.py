@@ -92,6 +92,12 @@ class Explainer:
         self._queries = {}      # per-query (prepare context, plan, arch check): _query_key
 
     @property
+    def attention_engine(self):
+        """params["attention_engine"] (default False): compile GATConv relations to the HIP
+        engine's attention kernels instead of running such archs on the generic torch path."""
+        return bool(self.params.get("attention_engine", False))
+
+    @property
     def edge_masks(self):
         """Non-compat edge problems (params["edge_masks"] = True): mask columns
         are the computational graph's edges (Data.perturb_edge, data.py:500-554) and the arch is
@@ -196,7 +202,8 @@ class Explainer:
         query-dependent lowering (ForwardPlan drops other destination types' relation terms from a
         layer whose targets share one node type, so two queries can lower the same module
         differently)."""
-        return (id(self.arch), state[0], state[1], self.edge_masks, bool(getattr(plan, "multi_type", False)),
+        return (id(self.arch), state[0], state[1], self.edge_masks, self.attention_engine,
+                bool(getattr(plan, "multi_type", False)),
                 tuple(c["h_ntypes"] or ()), tuple(c["h_etypes"] or ()),
                 tuple(getattr(plan, "lowering", ())))
 
@@ -206,7 +213,8 @@ class Explainer:
         business (prepare() draws no random numbers, so reusing its result leaves every RNG
         stream as the reference's)."""
         return (str(element), type(element).__name__, self.problem, self.edge_masks, str(device),
-                _freeze(self.element_type), str(self.params.get("verify_arch", True)))
+                _freeze(self.element_type), str(self.params.get("verify_arch", True)),
+                self.attention_engine)
 
     def _query_sources(self, params, bufs):
         """Identity snapshot of what prepare() and the query's ForwardPlan read: the graph and
@@ -462,7 +470,7 @@ class Explainer:
             verify = lambda: pipeline.verify_edge_plan(plan, self.arch, sub_feat, sub_ei, *c["link"])
         else:
             plan = pipeline.build_plan(self.arch, sub_feat, sub_ei, [sub_ind], *geo,
-                                       module_state=mstate)
+                                       module_state=mstate, attention=self.attention_engine)
             verify = lambda: pipeline.verify_plan(plan, self.arch, sub_feat, sub_ei, sub_ind, *geo)
         clock.mark("verify")
         arch_check = "off"
@@ -633,7 +641,8 @@ class Explainer:
         geo = (c["sub_nt"], c["sub_et"], c["h_ntypes"], c["h_etypes"], c["padded_dims"])
         Q = len(inds)
         assert len(set(inds)) == Q, "run_queries: duplicate query elements"
-        plan = pipeline.build_plan(self.arch, sub_feat, sub_ei, inds, *geo, module_state=mstate)
+        plan = pipeline.build_plan(self.arch, sub_feat, sub_ei, inds, *geo, module_state=mstate,
+                                   attention=self.attention_engine)
         assert plan is not None and not getattr(plan, "multi_type", False), \
             "run_queries needs an engine-compilable single-node-type architecture"
         if self.params.get("verify_arch", True):

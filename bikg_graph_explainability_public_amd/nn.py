@@ -146,7 +146,10 @@ class GATConv(MessagePassing):
     softmax over each target's in-edges of leaky_relu(a_src . h_j + a_dst . h_i, 0.2), heads
     concatenated (or averaged), + bias.  The conv of the reference's multi-node-type test arch
     (tests/test_utils.py:86-182: HeteroConv of GATConv((-1, -1), c, add_self_loops=False)).
-    The engine does not compile it: archs using it run on the generic (batched) path."""
+    By default archs using it run on the generic (batched) torch path; with the opt-in
+    (Explainer params["attention_engine"] = True, program.compile_arch(..., attention=True)) the
+    engine compiles it to its masked-attention HIP kernels (concat=True, or concat=False with
+    one head; no edge_dim)."""
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2,
                  dropout=0.0, add_self_loops=True, bias=True, **kwargs):
@@ -233,19 +236,37 @@ class HeteroConv(nn.Module):
 class ConvStack(nn.Module):
     """Model family of the reference tests/notebooks (tests/test_utils.py:10-83,
     examples/toy_example-caseA.ipynb cell 9): `conv` = ModuleList[Conv, ReLU]*, `fc` =
-    ModuleList[Linear, act]* ending in Sigmoid.  `kind` in {"gcn", "sage"}; `hetero_rels`
-    wraps each conv in HeteroConv over the given edge types (single node type)."""
+    ModuleList[Linear, act]* ending in Sigmoid.  `kind` in {"gcn", "sage", "gat"}; `hetero_rels`
+    wraps each conv in HeteroConv over the given edge types (single node type).  "gat":
+    GATConv layers with `heads[i]` concatenated heads of dims[i + 1] channels (default all 1), so
+    layer i reads dims[i] * heads[i - 1] columns and the head reads dims[-1] * heads[-1]."""
 
-    def __init__(self, kind, dims, fc_dims, hetero_rels=None, final_act="sigmoid"):
+    def __init__(self, kind, dims, fc_dims, hetero_rels=None, final_act="sigmoid", heads=None,
+                 add_self_loops=True):
         super().__init__()
-        mk = GCNConv if kind == "gcn" else SAGEConv
+        n_conv = len(dims) - 1
+        if kind == "gat":
+            heads = [1] * n_conv if heads is None else [int(h) for h in heads]
+            if len(heads) != n_conv:
+                raise ValueError("heads must give one entry per conv layer")
+
+            def mk(f_in, f_out, i):
+                return GATConv(f_in * (heads[i - 1] if i else 1), f_out, heads=heads[i],
+                               add_self_loops=add_self_loops)
+        else:
+            if heads is not None:
+                raise ValueError("heads applies to kind='gat' only")
+            cls = GCNConv if kind == "gcn" else SAGEConv
+
+            def mk(f_in, f_out, i):
+                return cls(f_in, f_out)
         convs = []
-        for i in range(len(dims) - 1):
+        for i in range(n_conv):
             if hetero_rels is not None:
-                convs.append(HeteroConv({tuple(r): mk(dims[i], dims[i + 1])
+                convs.append(HeteroConv({tuple(r): mk(dims[i], dims[i + 1], i)
                                          for r in hetero_rels}))
             else:
-                convs.append(mk(dims[i], dims[i + 1]))
+                convs.append(mk(dims[i], dims[i + 1], i))
             convs.append(nn.ReLU())
         self.conv = nn.ModuleList(convs)
         fcs = []
@@ -306,8 +327,10 @@ class HeteroGATStack(nn.Module):
     """Multi-node-type model family of the reference's own multi-type test arch
     (tests/test_utils.py:86-182: HeteroConv({(src, rel, dst): GATConv((-1, -1), c,
     add_self_loops=False)}, aggr="sum") -> ReLU, then Linear layers on the first output node
-    type), with explicit input widths per layer and `heads` per layer (concatenated).  The
-    engine does not compile GAT: it runs on the generic (batched) torch path.  state_dict keys:
+    type), with explicit input widths per layer and `heads` per layer (concatenated).  It runs
+    on the generic (batched) torch path unless the attention engine is opted into
+    (params["attention_engine"] = True; add_self_loops=False only on multi-type graphs).
+    state_dict keys:
     conv.<2l>.convs.<src>__<rel>__<dst>.{lin_src,lin_dst}.weight / att_src / att_dst / bias."""
 
     def __init__(self, rels, in_dims, hidden, heads, fc_dims, add_self_loops=False):

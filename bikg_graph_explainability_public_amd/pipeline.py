@@ -40,7 +40,8 @@ def clear_programs():
     _PROGRAMS.clear()
 
 
-def compiled_program(arch, edge_type_names=None, node_type_names=None, state=None):
+def compiled_program(arch, edge_type_names=None, node_type_names=None, state=None,
+                     attention=False):
     """compile_arch(arch, ...) once per module state: keyed by the module (identity, checked by
     weak reference), every parameter and buffer (storage + in-place version counter: an
     optimizer step, load_state_dict or a replaced tensor compiles again) and the type names.
@@ -55,12 +56,12 @@ def compiled_program(arch, edge_type_names=None, node_type_names=None, state=Non
                  tuple((t.data_ptr(), t._version) for t in arch.buffers()))
     key = (id(arch), state,
            tuple(tuple(e) for e in edge_type_names) if edge_type_names is not None else None,
-           tuple(node_type_names) if node_type_names is not None else None)
+           tuple(node_type_names) if node_type_names is not None else None, bool(attention))
     hit = _PROGRAMS.get(key)
     if hit is not None and hit[0]() is arch:
         _PROGRAMS.move_to_end(key)
         return hit[1]
-    prog = compile_arch(arch, edge_type_names, node_type_names)
+    prog = compile_arch(arch, edge_type_names, node_type_names, attention=bool(attention))
     _PROGRAMS[key] = (weakref.ref(arch), prog)
     while len(_PROGRAMS) > 8:
         _PROGRAMS.popitem(last=False)
@@ -68,8 +69,11 @@ def compiled_program(arch, edge_type_names=None, node_type_names=None, state=Non
 
 
 def build_plan(arch, feat, edge_index, queries, node_type=None, edge_type=None,
-               node_type_names=None, edge_type_names=None, padded_dims=None, module_state=None):
+               node_type_names=None, edge_type_names=None, padded_dims=None, module_state=None,
+               attention=False):
     """ForwardPlan for `arch` on the (sub)graph, or None when the engine cannot run it.
+    `attention=True` (opt-in, Explainer params["attention_engine"]) also compiles GATConv
+    relations, which otherwise run on the generic torch path.
 
     Multi-node-type graphs (model.py:118-253): the program's terms are gated by destination
     node type and the query is the reference's `out[sub_ind, 0]` — row sub_ind of the output
@@ -81,7 +85,8 @@ def build_plan(arch, feat, edge_index, queries, node_type=None, edge_type=None,
     hetero = edge_type_names is not None and edge_type is not None
     try:
         prog = compiled_program(arch, edge_type_names if hetero else None,
-                                node_type_names if multi else None, module_state)
+                                node_type_names if multi else None, module_state,
+                                attention=attention)
     except UnsupportedArch as e:
         warnings.warn(f"engine cannot compile arch ({e}); using the generic torch path")
         return None

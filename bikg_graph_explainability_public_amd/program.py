@@ -2,9 +2,9 @@
 
 The reference treats `arch` as a black box and calls `arch(feat, edge_index)` on the B-fold
 union graph (model.py:62-116).  The engine instead recognises the supported module family —
-GCNConv / SAGEConv (mean) / HeteroConv(sum) conv layers, each optionally followed by an
-elementwise activation, then Linear layers with activations (the layout of
-tests/test_utils.py:10-83 and the notebooks) — and lowers it to:
+GCNConv / SAGEConv (mean) / HeteroConv(sum) conv layers (and, with `attention=True`, GATConv),
+each optionally followed by an elementwise activation, then Linear layers with activations (the
+layout of tests/test_utils.py:10-83 and the notebooks) — and lowers it to:
 
     ConvLayer(terms=[(kind, relation, W_k)], bias_sum, act)   per conv layer
     HeadLayer(W, b, act)                                       per Linear
@@ -33,10 +33,18 @@ class UnsupportedArch(ValueError):
 
 @dataclass
 class Term:
-    kind: str          # "gcn" | "mean" | "root"
+    kind: str          # "gcn" | "mean" | "root" | "att"
     rel: int           # relation index (ignored for root)
-    weight: torch.Tensor  # [f_out, f_in]
+    weight: torch.Tensor  # [f_out, f_in] (att: W_src, [heads * head_ch, f_in])
     dst_type: int = -1    # multi-node-type: destination node type of the relation
+    # kind "att" (GATConv, PyG 2.0.4): one term per relation
+    heads: int = 1
+    head_ch: int = 0
+    att_src: Optional[torch.Tensor] = None     # [heads, head_ch]
+    att_dst: Optional[torch.Tensor] = None     # [heads, head_ch]
+    weight_dst: Optional[torch.Tensor] = None  # bipartite relations: W_dst; None: W_src for both ends
+    neg_slope: float = 0.2
+    self_loops: bool = False
 
 
 @dataclass
@@ -85,18 +93,23 @@ def _act_name(m):
     return _ACTS[name]
 
 
-def _is_conv(m):
-    return type(m).__name__ in ("GCNConv", "SAGEConv", "HeteroConv")
+def _is_gat(m):
+    return type(m).__name__ == "GATConv" and all(
+        hasattr(m, a) for a in ("lin_src", "lin_dst", "att_src", "att_dst", "heads", "out_channels"))
+
+
+def _is_conv(m, attention=False):
+    return type(m).__name__ in ("GCNConv", "SAGEConv", "HeteroConv") or (attention and _is_gat(m))
 
 
 def _is_linear(m):
     return type(m).__name__ == "Linear" and hasattr(m, "weight")
 
 
-def _leaf_units(module):
+def _leaf_units(module, attention=False):
     """Registration-order walk yielding conv / linear / activation units (convs not entered)."""
     for child in module.children():
-        if _is_conv(child) or _is_linear(child) or _act_name(child) is not None:
+        if _is_conv(child, attention) or _is_linear(child) or _act_name(child) is not None:
             yield child
         elif type(child).__name__ in _SKIP:
             continue
@@ -105,15 +118,95 @@ def _leaf_units(module):
                 raise UnsupportedArch(f"unsupported parameterised module {type(child).__name__}")
             continue
         else:
-            yield from _leaf_units(child)
+            yield from _leaf_units(child, attention)
 
 
 def _f32(t):
     return t.detach().to(torch.float32)
 
 
-def _single_conv_terms(conv, rel):
+def _gat_terms(conv, rel, bipartite):
+    """One GATConv relation as an "att" term.  A same-type relation is handed a Tensor by
+    HeteroConv and 2.0.4 then transforms both ends with lin_src, even when a separate lin_dst
+    exists; lin_dst is used by bipartite relations only."""
+    H, C = int(conv.heads), int(conv.out_channels)
+    concat = bool(getattr(conv, "concat", True))
+    if not concat and H > 1:
+        raise UnsupportedArch("GATConv(concat=False) with several heads")
+    if getattr(conv, "edge_dim", None) is not None or getattr(conv, "lin_edge", None) is not None:
+        raise UnsupportedArch("GATConv with edge_dim")
+    for lin in (conv.lin_src, conv.lin_dst):
+        if isinstance(getattr(lin, "weight", None), nn.parameter.UninitializedParameter):
+            raise UnsupportedArch("GATConv with uninitialised (lazy) weights")
+        if getattr(lin, "bias", None) is not None:
+            raise UnsupportedArch("GATConv.lin_src / lin_dst with bias")
+    W = _f32(conv.lin_src.weight)
+    if W.shape[0] != H * C:
+        raise UnsupportedArch("GATConv weight shape does not match heads * out_channels")
+    Wd = None
+    if bipartite and conv.lin_dst is not conv.lin_src:
+        Wd = _f32(conv.lin_dst.weight)
+        if Wd.shape[0] != H * C:
+            raise UnsupportedArch("GATConv lin_dst shape does not match heads * out_channels")
+    b = _f32(conv.bias) if getattr(conv, "bias", None) is not None else None
+    term = Term("att", rel, W, heads=H, head_ch=C,
+                att_src=_f32(conv.att_src).reshape(H, C), att_dst=_f32(conv.att_dst).reshape(H, C),
+                weight_dst=Wd, neg_slope=float(getattr(conv, "negative_slope", 0.2)),
+                self_loops=bool(getattr(conv, "add_self_loops", True)))
+    return [term], b, None, W.shape[1], H * C
+
+
+def fold_attention(term):
+    """The attention vectors of an "att" term folded through its weights: (v_s, v_d), each
+    [heads, f_in], with v_s[h] = W_src[hC:(h+1)C, :]^T att_src[h] (v_d likewise, with W_dst for
+    bipartite relations), so that v_s[h] . x == att_src[h] . (W_src x)[hC:(h+1)C]: the scores of
+    layer-input rows without the transformed rows.  Pure torch, any device / dtype."""
+    H, C = term.heads, term.head_ch
+    Ws = term.weight
+    Wd = term.weight_dst if term.weight_dst is not None else Ws
+    att_s = term.att_src.to(Ws.dtype).to(Ws.device)
+    att_d = term.att_dst.to(Wd.dtype).to(Wd.device)
+    v_s = torch.einsum("hcf,hc->hf", Ws.reshape(H, C, -1), att_s)
+    v_d = torch.einsum("hcf,hc->hf", Wd.reshape(H, C, -1), att_d)
+    return v_s, v_d
+
+
+def stack_attention(terms, f_in_pad, f_out_pad):
+    """The dense weight and padded score vectors of an all-"att" layer past the first, which
+    keeps the engine's aggregate-then-transform form: the layer's dense input holds one
+    f_in_pad-wide slice per (term, head), slice (k, h) = sum_e alpha_e^h (input row of e's
+    source), and Wc [f_out_pad, slices * f_in_pad] has W_src[hC:(h+1)C, :] in rows hC..(h+1)C of
+    slice (k, h) and zeros elsewhere, so Wc times the slices equals the per-head transform of the
+    aggregates (= aggregating the transformed rows).  Returns (Wc, [(v_s, v_d)] per term, each
+    [heads, f_in_pad], zero-padded `fold_attention` vectors).  Pure torch, dtype of the weights."""
+    n_sl = sum(t.heads for t in terms)
+    W0 = terms[0].weight
+    wc = torch.zeros((f_out_pad, n_sl * f_in_pad), dtype=W0.dtype, device=W0.device)
+    vecs, sl = [], 0
+    for term in terms:
+        C, W = term.head_ch, term.weight
+        f_in = W.shape[1]
+        for h in range(term.heads):
+            wc[h * C:(h + 1) * C, sl * f_in_pad:sl * f_in_pad + f_in] = W[h * C:(h + 1) * C]
+            sl += 1
+        pair = []
+        for v in fold_attention(term):
+            vp = torch.zeros((term.heads, f_in_pad), dtype=v.dtype, device=v.device)
+            vp[:, :f_in] = v
+            pair.append(vp)
+        vecs.append(tuple(pair))
+    return wc, vecs
+
+
+def _check_unmixed(terms):
+    if any(t.kind == "att" for t in terms) and not all(t.kind == "att" for t in terms):
+        raise UnsupportedArch("a conv layer mixing GATConv with GCNConv / SAGEConv relations")
+
+
+def _single_conv_terms(conv, rel, attention=False, bipartite=False):
     name = type(conv).__name__
+    if attention and _is_gat(conv):
+        return _gat_terms(conv, rel, bipartite)
     if name == "GCNConv":
         if getattr(conv, "improved", False) or not getattr(conv, "add_self_loops", True) \
                 or not getattr(conv, "normalize", True):
@@ -135,7 +228,7 @@ def _single_conv_terms(conv, rel):
     raise UnsupportedArch(f"unsupported conv {name}")
 
 
-def _conv_layer(conv, rel_index):
+def _conv_layer(conv, rel_index, attention=False):
     """Lower one conv (or HeteroConv) to terms.  rel_index maps edge-type tuples to relations."""
     if type(conv).__name__ == "HeteroConv":
         if getattr(conv, "aggr", "sum") != "sum":
@@ -150,7 +243,9 @@ def _conv_layer(conv, rel_index):
                 continue  # relation absent from the graph: HeteroConv skips it too
             if et[0] != et[-1]:
                 raise UnsupportedArch("bipartite relations need the multi-node-type path")
-            t, b, wr, fi, fo = _single_conv_terms(sub, rel_index[et])
+            t, b, wr, fi, fo = _single_conv_terms(sub, rel_index[et], attention)
+            if f_out is not None and fo != f_out and (t[0].kind == "att" or terms[0].kind == "att"):
+                raise UnsupportedArch("HeteroConv relations with different output widths")
             terms += t
             if b is not None:
                 bias = b.clone() if bias is None else bias + b
@@ -162,7 +257,8 @@ def _conv_layer(conv, rel_index):
     else:
         if rel_index is not None and len(rel_index) != 1:
             raise UnsupportedArch("homogeneous conv on a multi-relation graph")
-        terms, bias, root, f_in, f_out = _single_conv_terms(conv, 0)
+        terms, bias, root, f_in, f_out = _single_conv_terms(conv, 0, attention)
+    _check_unmixed(terms)
     if root is not None:
         terms.append(Term("root", -1, root))
     if bias is None:
@@ -174,7 +270,7 @@ def _pad_cols(w, n):
     return w if w.shape[1] == n else torch.nn.functional.pad(w, (0, n - w.shape[1]))
 
 
-def _conv_layer_multi(conv, rel_index, node_type_names):
+def _conv_layer_multi(conv, rel_index, node_type_names, attention=False):
     """HeteroConv over several node types: terms gated by destination type, SAGE root weights
     and biases summed per destination type.  Returns (terms, bias [n_types, f_out], f_in, f_out,
     destination type of the first present relation)."""
@@ -190,7 +286,9 @@ def _conv_layer_multi(conv, rel_index, node_type_names):
         s_t, d_t = node_type_names.index(et[0]), node_type_names.index(et[-1])
         if type(sub).__name__ == "GCNConv" and s_t != d_t:
             raise UnsupportedArch("GCNConv on a bipartite relation")
-        t, b, wr, fi, fo = _single_conv_terms(sub, rel_index[et])
+        t, b, wr, fi, fo = _single_conv_terms(sub, rel_index[et], attention, s_t != d_t)
+        if t[0].kind == "att" and t[0].self_loops:
+            raise UnsupportedArch("GATConv(add_self_loops=True) on a multi-node-type graph")
         if f_out is not None and fo != f_out:
             raise UnsupportedArch("HeteroConv relations with different output widths")
         f_out = fo
@@ -198,6 +296,8 @@ def _conv_layer_multi(conv, rel_index, node_type_names):
         for term in t:
             term.dst_type = d_t
             f_ins.append(term.weight.shape[1])
+            if term.weight_dst is not None:
+                f_ins.append(term.weight_dst.shape[1])
         terms += t
         if b is not None:
             biases[d_t] = b.clone() if d_t not in biases else biases[d_t] + b
@@ -208,6 +308,7 @@ def _conv_layer_multi(conv, rel_index, node_type_names):
             roots[d_t] = wr.clone() if d_t not in roots else roots[d_t] + wr
     if not terms:
         raise UnsupportedArch("HeteroConv with no relation present in the graph")
+    _check_unmixed(terms)
     # HeteroConv's output dict is keyed in edge_index_dict order (the graph's relation order)
     for et in rel_index:
         if "__".join(et) in conv.convs:
@@ -218,18 +319,23 @@ def _conv_layer_multi(conv, rel_index, node_type_names):
     f_in = max(f_ins)
     for term in terms:
         term.weight = _pad_cols(term.weight, f_in)
+        if term.weight_dst is not None:
+            term.weight_dst = _pad_cols(term.weight_dst, f_in)
     bias = torch.zeros(nt, f_out)
     for d_t, b in biases.items():
         bias[d_t] = b
     return terms, bias, f_in, f_out, first_dst
 
 
-def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None) -> ModelProgram:
+def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
+                 attention=False) -> ModelProgram:
     """Lower `arch` to a ModelProgram.  `edge_type_names` (list of (src, rel, dst) tuples in
     homogenised edge-type order, data.py:743-822) enables HeteroConv relations;
-    `node_type_names` with two or more types selects the multi-node-type lowering."""
+    `node_type_names` with two or more types selects the multi-node-type lowering.
+    `attention=True` (opt-in) also lowers GATConv relations, to "att" terms; by default an
+    arch with GATConv raises UnsupportedArch."""
     if type(arch).__name__ == "LinkModel" and hasattr(arch, "encoder"):
-        prog = compile_arch(arch.encoder, edge_type_names, node_type_names)
+        prog = compile_arch(arch.encoder, edge_type_names, node_type_names, attention)
         prog.link_act = getattr(arch, "act", "identity") or "identity"
         return prog
     rel_index = None
@@ -238,17 +344,17 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None) ->
     multi = node_type_names is not None and len(node_type_names) >= 2
     if multi and rel_index is None:
         raise UnsupportedArch("multi-node-type graphs need edge types")
-    units = list(_leaf_units(arch))
+    units = list(_leaf_units(arch, attention))
     prog = ModelProgram()
     if multi:
         prog.n_types = len(node_type_names)
     i = 0
-    while i < len(units) and _is_conv(units[i]):
+    while i < len(units) and _is_conv(units[i], attention):
         if multi:
-            terms, bias, f_in, f_out, prog.out_type = _conv_layer_multi(units[i], rel_index,
-                                                                        list(node_type_names))
+            terms, bias, f_in, f_out, prog.out_type = _conv_layer_multi(
+                units[i], rel_index, list(node_type_names), attention)
         else:
-            terms, bias, f_in, f_out = _conv_layer(units[i], rel_index)
+            terms, bias, f_in, f_out = _conv_layer(units[i], rel_index, attention)
         act = None
         if i + 1 < len(units) and _act_name(units[i + 1]) is not None:
             act = _act_name(units[i + 1])

@@ -29,8 +29,8 @@
  *   xpg_popcount_rows + xpg_shap_kernel— Kernel.compute             kernels.py:115-174
  *   xpg_masked_forward                 — Data.perturbator + Model.infer + extract_node_edge_output
  *                                        (wlm.py:349-436 -> data.py:591-648, model.py:62-116,
- *                                        model.py:295-328) for GCNConv / SAGEConv / HeteroConv-sum
- *                                        conv stacks with a dense head; with edge_masks set, the
+ *                                        model.py:295-328) for GCNConv / SAGEConv / GATConv /
+ *                                        HeteroConv-sum conv stacks with a dense head; with edge_masks set, the
  *                                        edge problem's Data.perturb_edge (data.py:500-554: mask
  *                                        columns are edges) and a dot-product link decoder
  *   xpg_dense                          — the dense feature x weight contraction inside each layer
@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define XPG_ABI_VERSION 21
+#define XPG_ABI_VERSION 22
 #define XPG_MAX_TERMS 8
 
 typedef void* xpg_stream_t; /* hipStream_t */
@@ -62,7 +62,8 @@ enum xpg_act { XPG_ACT_NONE = 0, XPG_ACT_RELU = 1, XPG_ACT_SIGMOID = 2, XPG_ACT_
 /* aggregation term kinds of one conv layer (one term per relation, plus ROOT for SAGE) */
 enum xpg_term { XPG_TERM_GCN = 0,   /* D^-1/2 (A_r + I) D^-1/2 over relation r               */
                 XPG_TERM_MEAN = 1,  /* mean over kept in-edges of relation r (SAGE aggr)      */
-                XPG_TERM_ROOT = 2   /* the target's own row (SAGE lin_r)                     */ };
+                XPG_TERM_ROOT = 2,  /* the target's own row (SAGE lin_r)                     */
+                XPG_TERM_ATT = 3    /* graph attention over relation r (GATConv, v22; below)  */ };
 
 int xpg_abi_version(void);
 const char* xpg_last_error(void);
@@ -194,6 +195,28 @@ typedef struct xpg_term_desc {
   const float* table;      /* layer 1 only: pre-transformed F_0 rows [n0][f_out_pad]   */
   int32_t dst_type;        /* multi-node-type plans: the term only reaches targets of   */
                            /* this node type (HeteroConv relation destination); -1 = all */
+  /* XPG_TERM_ATT only (v22): one term = one GATConv relation (PyG 2.0.4 semantics) with `heads`
+   * heads of `head_ch` channels, heads * head_ch = the conv's output width.
+   * Edge set of target t in mask row b (node masks only): a non-self in-edge (u -> t) takes part
+   * iff bit(b, u) & bit(b, t), duplicate edges as separate entries; self_loops = 0: the
+   * self_mult copies of (t -> t) take part as ordinary edges iff bit(b, t); self_loops = 1
+   * (add_self_loops): existing self-loops are dropped and exactly one (t -> t) edge takes part
+   * whatever the mask.
+   * Logit of edge e = (u -> t), head h: z = leaky_relu(a_s[u, h] + a_d[t, h], neg_slope);
+   * softmax over the edge set: m = max z, p_e = exp(z_e - m), alpha_e = p_e / (sum p + 1e-16);
+   * an empty edge set gives 0.
+   * Layer 1: att_src / att_dst = [n0][heads] score tables a_s / a_d of the F_0 nodes (shared by
+   * every mask row) and the term adds sum_e alpha_e table[u][h * head_ch + c] to column
+   * h * head_ch + c.  Layer >= 2: att_src / att_dst = [heads][f_in_pad] vectors v_s / v_d with
+   * a_s[u, h] = <v_s[h], row u of the layer input> (a_d likewise on the target's row), and the
+   * term fills `heads` slices of the layer's dense input, slice h = sum_e alpha_e^h (row u);
+   * the layer's `weight` then has one f_in_pad-wide column block per slice, in term order.
+   * A layer's terms are all ATT or none; ATT plans run on the multi-kernel path only.       */
+  int32_t heads, head_ch;
+  float neg_slope;         /* leaky_relu slope of the logits (GATConv negative_slope)      */
+  int32_t self_loops;      /* GATConv add_self_loops                                      */
+  const float* att_src;
+  const float* att_dst;
 } xpg_term_desc;
 
 typedef struct xpg_layer_desc {
@@ -213,7 +236,8 @@ typedef struct xpg_layer_desc {
   const int32_t* agg_f0;   /* source positions inside F_0                              */
   const int32_t* self_mult;/* [n_rel * n_tgt] multiplicity of (t, t) edges             */
   xpg_term_desc terms[XPG_MAX_TERMS];
-  const float* weight;     /* layer >= 2: [f_out_pad][n_terms * f_in_pad]               */
+  const float* weight;     /* layer >= 2: [f_out_pad][n_terms * f_in_pad] (ATT layers:   */
+                           /* [f_out_pad][(sum of the terms' heads) * f_in_pad])         */
   const float* bias;       /* [n_types][f_out_pad], summed over relations, zero-padded */
   const int32_t* tgt_type; /* multi-node-type plans: [n_tgt] node type of each target;   */
                            /* NULL for homogeneous / single-node-type graphs             */
