@@ -11,7 +11,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libxpgnn.so")
-ABI_VERSION = 22
+ABI_VERSION = 23
 MAX_TERMS = 8
 
 ACT = {None: 0, "identity": 0, "relu": 1, "sigmoid": 2, "tanh": 3, "leaky_relu": 4, "elu": 5}
@@ -95,6 +95,9 @@ _SIGS = {
                                ctypes.POINTER(ctypes.c_size_t)], c_i32),
     "xpg_masked_forward": ([ctypes.POINTER(ForwardPlanDesc), c_vp, c_i64, c_vp, c_vp,
                             ctypes.c_size_t, c_vp], c_i32),
+    "xpg_forward_describe": ([ctypes.POINTER(ForwardPlanDesc), c_i64, ctypes.c_char_p,
+                              ctypes.c_size_t], c_i32),
+    "xpg_wide_variants": ([ctypes.c_char_p, ctypes.c_size_t], c_i32),
     "xpg_profile_enable": ([ctypes.c_int], c_i32),
     "xpg_profile_read": ([c_vp, c_vp, c_i32], c_i32),
     "xpg_wlm_workspace": ([c_i64, c_i64, c_i64, c_i64, ctypes.POINTER(ctypes.c_size_t)], c_i32),

@@ -5993,8 +5993,10 @@ bool forward_is(const char* v) {
   return v ? env && std::strcmp(env, v) == 0 : env && *env;
 }
 
-// Fused single-launch forward when the plan fits (returns 1 when it does not apply).
-int try_fused_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t rows, float* y, hipStream_t st) {
+// Fused single-launch forward when the plan fits (returns 1 when it does not apply).  `dry`: the
+// decision only (XPG_OK = the kernel takes the plan), nothing launched, no device touched.
+int try_fused_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t rows, float* y, hipStream_t st,
+                      bool dry = false) {
   // opt-in (XPG_FORWARD=fused): per-row latency chains make it slower than k_rows_forward
   if (!forward_is("fused")) return 1;
   if (plan_has_attention(p)) return 1;  // attention: multi-kernel path only
@@ -6087,6 +6089,7 @@ int try_fused_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t r
     }
   }
   if (!wpb) return 1;
+  if (dry) return XPG_OK;
   const size_t lds = sizeof(float) * (size_t)(shared + (int64_t)wpb * a.wave_floats);
   const int64_t per_cu = std::max<int64_t>(1, (160 * 1024) / (int64_t)lds);
   const int64_t grid = std::min<int64_t>(cdiv(rows, wpb), 256 * per_cu);
@@ -6210,7 +6213,9 @@ int wide_layout(const xpg_forward_plan* p, int64_t rows, WideWs* W) {
   W->lds = sizeof(float) * (size_t)off_f;
   if (W->lds > 150 * 1024) return 1;
   W->kw = 0;  // layer weights in registers (one 32-column block per wave) when they fit
-  if (l2.f_out_pad <= 128 && (K == 32 || K == 64 || K == 128)) W->kw = K / 8;
+  // (four 32-wide terms, e.g. three SAGE or four GCN relations at hidden 32, have K = 128 but no
+  // 16-register variant at nfi 2: they stream their weights like every other K)
+  if (l2.f_out_pad <= 128 && (K == 32 || K == 64 || K == 128) && !(W->nfi == 2 && K == 128)) W->kw = K / 8;
   size_t off = 0;
   W->mT = off;
   off += align_up(sizeof(uint32_t) * (size_t)p->cols);
@@ -6272,20 +6277,110 @@ bool wide_wanted(const xpg_forward_plan* p) {
   return p->n_layers == 2 && p->layers[0].n_tgt >= 8192;
 }
 
-template <bool LAST>
-void (*wide_kernel(int nfi, int kw))(WideArgs) {
-#define XPG_WK(NFI, KW) \
-  if (nfi == NFI && kw == KW) return k_wide_tgt<NFI, LAST, KW>;
-  if constexpr (LAST) {
-    XPG_WK(2, 4) XPG_WK(2, 8) XPG_WK(4, 8) XPG_WK(4, 16) XPG_WK(8, 16)
-  }
-  XPG_WK(2, 0) XPG_WK(4, 0) XPG_WK(8, 0) XPG_WK(12, 0) XPG_WK(16, 0)
-#undef XPG_WK
+// Every kernel the wide path can launch, by the name xpg_forward_describe reports.  wide_select
+// (the one selection, shared by the launch and by the query) returns rows of these two tables, so
+// no kernel runs that xpg_wide_variants does not list.  Keys: layer 1 {1, width / 64, gcn} for
+// k_wide_l1s and {0, nfi, 0} for the gather kernel; layer 2 {0, nfi, kw} for k_wide_tgt and
+// {1, nfi, kw32 + 2 * b3 + 4 * pipe} for the warp-specialised kernel.
+struct WideVariant {
+  void (*fn)(WideArgs);
+  const char* name;
+  int kind, x, y;
+};
+#define XPG_WV_TGT(NFI, LAST, KW) {k_wide_tgt<NFI, LAST, KW>, "k_wide_tgt<" #NFI "," #LAST "," #KW ">", 0, NFI, KW}
+#define XPG_WV_L1S(FPL, GCN) {k_wide_l1s<FPL, GCN>, "k_wide_l1s<" #FPL "," #GCN ">", 1, FPL, GCN}
+const WideVariant kWideL1[] = {
+    XPG_WV_L1S(1, 0), XPG_WV_L1S(1, 1), XPG_WV_L1S(2, 0), XPG_WV_L1S(2, 1), XPG_WV_L1S(4, 0), XPG_WV_L1S(4, 1),
+    XPG_WV_TGT(2, 0, 0), XPG_WV_TGT(4, 0, 0), XPG_WV_TGT(8, 0, 0), XPG_WV_TGT(12, 0, 0), XPG_WV_TGT(16, 0, 0),
+};
+const WideVariant kWideL2[] = {
+    XPG_WV_TGT(2, 1, 4), XPG_WV_TGT(2, 1, 8), XPG_WV_TGT(4, 1, 8), XPG_WV_TGT(4, 1, 16), XPG_WV_TGT(8, 1, 16),
+    XPG_WV_TGT(2, 1, 0), XPG_WV_TGT(4, 1, 0), XPG_WV_TGT(8, 1, 0), XPG_WV_TGT(12, 1, 0), XPG_WV_TGT(16, 1, 0),
+    {k_wide_last_ws<8, 32, 8, true, 1, true, 8, true, true>, "k_wide_last_ws<8,32,8,1,pipe>", 1, 8, 7},
+    {k_wide_last_ws<8, 32, 8, true>, "k_wide_last_ws<8,32,8,1>", 1, 8, 3},
+    {k_wide_last_ws<8, 32, 8>, "k_wide_last_ws<8,32,8,0>", 1, 8, 1},
+    {k_wide_last_ws<8, 0, 8>, "k_wide_last_ws<8,0,8,0>", 1, 8, 0},
+    {k_wide_last_ws<4, 32, 8>, "k_wide_last_ws<4,32,8,0>", 1, 4, 1},
+    {k_wide_last_ws<4, 0, 8>, "k_wide_last_ws<4,0,8,0>", 1, 4, 0},
+};
+#undef XPG_WV_TGT
+#undef XPG_WV_L1S
+template <size_t N>
+const WideVariant* wide_variant(const WideVariant (&tab)[N], int kind, int x, int y) {
+  for (const WideVariant& v : tab)
+    if (v.kind == kind && v.x == x && v.y == y) return &v;
   return nullptr;
+}
+
+// The wide path's kernel choice for a plan wide_layout took (host only: plan fields and the
+// environment).
+struct WidePick {
+  const WideVariant* k1;
+  const WideVariant* k2;
+  int dbg;      // XPG_WIDE_DBG
+  int agg1;     // layer 2's aggregating term when it has exactly one, else -1
+  bool head1;   // single-logit head fused into the layer-2 epilogue
+  bool l1s_k;   // layer 1 is a k_wide_l1s
+  bool ws2;     // layer 2 is a k_wide_last_ws
+  bool b3, pipe;
+};
+
+int wide_select(const xpg_forward_plan* p, const WideWs& W, WidePick* s) {
+  const xpg_layer_desc& l1 = p->layers[0];
+  const xpg_layer_desc& l2 = p->layers[1];
+  if (const int rc = diag_env("XPG_WIDE_DBG", &s->dbg)) return rc;
+  int nagg = 0;
+  s->agg1 = -1;
+  for (int k = 0; k < l2.n_terms; ++k)
+    if (l2.terms[k].kind != XPG_TERM_ROOT) {
+      ++nagg;
+      s->agg1 = k;
+    }
+  if (nagg != 1) s->agg1 = -1;
+  s->head1 = p->n_head == 1 && p->head[0].n_real == 1 && p->out_col == 0;
+  // layer 1: one wave per target for all 32 samples, each table row read once (k_wide_l1s,
+  // widths 64 / 128 / 256) when term 0 aggregates and the others are ROOT, else the 16-lane-group
+  // gather kernel (XPG_WIDE_L1_GATHER=1, a diagnostics switch, forces it: its parity suite)
+  int l1_gather = 0;
+  if (const int rc = diag_env("XPG_WIDE_L1_GATHER", &l1_gather)) return rc;
+  s->k1 = wide_variant(kWideL1, 0, l1.f_out_pad / 16, 0);
+  bool l1s_ok = l1.n_terms >= 1 && l1.terms[0].kind != XPG_TERM_ROOT;  // term 0 aggregates, the rest ROOT
+  for (int k = 1; k < l1.n_terms; ++k) l1s_ok &= l1.terms[k].kind == XPG_TERM_ROOT;
+  s->l1s_k = false;
+  if (!l1_gather && l1s_ok && (l1.f_out_pad == 64 || l1.f_out_pad == 128 || l1.f_out_pad == 256)) {
+    s->k1 = wide_variant(kWideL1, 1, l1.f_out_pad / 64, l1.terms[0].kind == XPG_TERM_GCN ? 1 : 0);
+    s->l1s_k = true;
+  }
+  s->k2 = wide_variant(kWideL2, 0, l2.f_in_pad / 16, W.kw);
+  if (!s->k1 || !s->k2) return fail(XPG_EINVAL, "wide forward: unsupported layer width");
+  // warp-specialised layer 2 (8 gather waves || 4 MFMA waves) for single-logit heads over one
+  // aggregating term; K = 256 (two 128-wide terms: SAGE): the MFMA waves hold their weight
+  // columns in registers and run the products as three bf16 MFMAs (XPG_WIDE_B3=0: the exact f32
+  // MFMA, the parity reference of the split products)
+  const int K = l2.n_terms * l2.f_in_pad;
+  const int nfi2 = l2.f_in_pad / 16;
+  s->ws2 = s->head1 && W.kw == 0 && s->agg1 >= 0 && l2.f_out_pad <= 128 && (nfi2 == 4 || nfi2 == 8) &&
+           !(s->dbg & 15);
+  const bool kw32 = K == 256;
+  const char* b3e = getenv("XPG_WIDE_B3");
+  s->b3 = kw32 && nfi2 == 8 && !(b3e && std::strcmp(b3e, "0") == 0);
+  // SAGE-shaped plans ({MEAN, ROOT}) with the B3 products: the pipelined gather with shared
+  // in-edge lists (the index chain once per workgroup), 8 prefetched kept rows per group, the
+  // transposed product with the in-lane head epilogue, active samples first and the next
+  // target's rows issued early (DESIGN.md §4, §6)
+  s->pipe = s->b3 && l2.n_terms == 2 && s->agg1 >= 0 && l2.terms[s->agg1].kind == XPG_TERM_MEAN &&
+            l2.terms[1 - s->agg1].kind == XPG_TERM_ROOT;
+  if (s->ws2) {
+    s->k2 = wide_variant(kWideL2, 1, nfi2, (kw32 ? 1 : 0) + (s->b3 ? 2 : 0) + (s->pipe ? 4 : 0));
+    if (!s->k2) return fail(XPG_EINVAL, "wide forward: unsupported layer width");
+  }
+  return XPG_OK;
 }
 
 int run_wide_forward(const xpg_forward_plan* p, const WideWs& W, const uint32_t* bits, int64_t rows, float* y,
                      char* ws, hipStream_t st) {
+  WidePick pick;
+  if (const int rc = wide_select(p, W, &pick)) return rc;
   const xpg_layer_desc& l1 = p->layers[0];
   const xpg_layer_desc& l2 = p->layers[1];
   const int words = words_of(p->cols);
@@ -6325,7 +6420,7 @@ int run_wide_forward(const xpg_forward_plan* p, const WideWs& W, const uint32_t*
   };
   WideArgs a1{}, a2{};
   fill(a1, l1);
-  if (const int rc = diag_env("XPG_WIDE_DBG", &a1.dbg)) return rc;
+  a1.dbg = pick.dbg;
   a1.n_src = p->n0;
   a1.w_row = l1.f_out_pad;
   a1.rstride = l1.f_out_pad;
@@ -6333,6 +6428,7 @@ int run_wide_forward(const xpg_forward_plan* p, const WideWs& W, const uint32_t*
   a1.o_e = 0;
   a1.out = h1;
   fill(a2, l2);
+  a2.agg1 = pick.agg1;
   a2.dbg = a1.dbg;
   a2.n_src = l1.n_tgt;
   a2.w_row = l2.f_in_pad;
@@ -6357,54 +6453,19 @@ int run_wide_forward(const xpg_forward_plan* p, const WideWs& W, const uint32_t*
     a2.H[i].bias = p->head[i].bias;
   }
   a2.weight = l2.weight;
-  a2.head1 = p->n_head == 1 && p->head[0].n_real == 1 && p->out_col == 0;
+  a2.head1 = pick.head1;
   a2.src = h1;
   a2.out = y;
-  // layer 1: one wave per target for all 32 samples, each table row read once (k_wide_l1s,
-  // widths 64 / 128 / 256) when term 0 aggregates and the others are ROOT, else the 16-lane-group
-  // gather kernel (XPG_WIDE_L1_GATHER=1, a diagnostics switch, forces it: its parity suite)
-  int l1_gather = 0;
-  if (const int rc = diag_env("XPG_WIDE_L1_GATHER", &l1_gather)) return rc;
-  void (*k1)(WideArgs) = wide_kernel<false>(l1.f_out_pad / 16, 0);
-  bool l1s_ok = a1.n_terms >= 1 && a1.kind[0] != XPG_TERM_ROOT;  // term 0 aggregates, the rest ROOT
-  for (int k = 1; k < a1.n_terms; ++k) l1s_ok &= a1.kind[k] == XPG_TERM_ROOT;
-  if (!l1_gather && l1s_ok) {
-    const bool g = a1.kind[0] == XPG_TERM_GCN;
-    if (l1.f_out_pad == 64) k1 = g ? k_wide_l1s<1, true> : k_wide_l1s<1, false>;
-    else if (l1.f_out_pad == 128) k1 = g ? k_wide_l1s<2, true> : k_wide_l1s<2, false>;
-    else if (l1.f_out_pad == 256) k1 = g ? k_wide_l1s<4, true> : k_wide_l1s<4, false>;
-  }
-  void (*k2)(WideArgs) = wide_kernel<true>(l2.f_in_pad / 16, W.kw);
-  if (!k1 || !k2) return fail(XPG_EINVAL, "wide forward: unsupported layer width");
-  // warp-specialised layer 2 (8 gather waves || 4 MFMA waves) for single-logit heads over one
-  // aggregating term; K = 256 (two 128-wide terms: SAGE): the MFMA waves hold their weight
-  // columns in registers and run the products as three bf16 MFMAs (XPG_WIDE_B3=0: the exact f32
-  // MFMA, the parity reference of the split products)
-  const int nfi2 = l2.f_in_pad / 16;
-  const bool ws2 = a2.head1 && W.kw == 0 && a2.agg1 >= 0 && l2.f_out_pad <= 128 && (nfi2 == 4 || nfi2 == 8) &&
-                   !(a2.dbg & 15);
-  const bool kw32 = a2.K == 256;
-  const char* b3e = getenv("XPG_WIDE_B3");
-  const bool b3 = kw32 && nfi2 == 8 && !(b3e && std::strcmp(b3e, "0") == 0);
+  void (*k1)(WideArgs) = pick.k1->fn;
+  void (*k2)(WideArgs) = pick.k2->fn;
+  const bool ws2 = pick.ws2, b3 = pick.b3, pipe = pick.pipe;
   const size_t lds_ws = sizeof(float) * (size_t)(2 * (b3 ? 32 * (a2.K + 8) : 32 * W.a_ld) + 2 * l2.f_out_pad) +
                         (b3 ? sizeof(uint16_t) * (size_t)a2.K * l2.f_out_pad : 0);  // weight lo pieces (bf16)
-  // SAGE-shaped plans ({MEAN, ROOT}) with the B3 products: the pipelined gather with shared
-  // in-edge lists (the index chain once per workgroup), 8 prefetched kept rows per group, the
-  // transposed product with the in-lane head epilogue, active samples first and the next
-  // target's rows issued early (DESIGN.md §4, §6)
-  const bool pipe = b3 && a2.n_terms == 2 && a2.agg1 >= 0 && a2.kind[a2.agg1] == XPG_TERM_MEAN &&
-                    a2.kind[1 - a2.agg1] == XPG_TERM_ROOT;
   a2.sort_samples = pipe ? 1 : 0;
   a2.early_prefetch = pipe ? 1 : 0;
-  if (ws2) {
-    if (pipe) k2 = k_wide_last_ws<8, 32, 8, true, 1, true, 8, true, true>;
-    else k2 = nfi2 == 8 ? (b3 ? k_wide_last_ws<8, 32, 8, true> : kw32 ? k_wide_last_ws<8, 32, 8> : k_wide_last_ws<8, 0, 8>)
-                        : (kw32 ? k_wide_last_ws<4, 32, 8> : k_wide_last_ws<4, 0, 8>);
-  }
   // inactive-row table for the default pair k_wide_l1s -> k_wide_last_ws; the other kernels
   // read / write h1 only
-  const bool l1s_k = k1 == k_wide_l1s<1, true> || k1 == k_wide_l1s<1, false> || k1 == k_wide_l1s<2, true> ||
-                     k1 == k_wide_l1s<2, false> || k1 == k_wide_l1s<4, true> || k1 == k_wide_l1s<4, false>;
+  const bool l1s_k = pick.l1s_k;
   const bool use_ct = ws2 && l1s_k;
   // kept in-degrees (k_wide_degree) are read by GCN terms and by the gather layer 1's MEAN
   // counts; k_wide_l1s and the layer-2 kernels count a MEAN term's kept edges themselves (SAGE:
@@ -6499,9 +6560,10 @@ int run_wide_forward(const xpg_forward_plan* p, const WideWs& W, const uint32_t*
   return XPG_OK;
 }
 
-// Lanes-=-rows fused forward for 1- and 2-layer plans (returns 1 when it does not apply).
+// Lanes-=-rows fused forward for 1- and 2-layer plans (returns 1 when it does not apply).  `dry`:
+// the decision only (XPG_OK = the kernel takes the plan), nothing launched, no device touched.
 int try_rows_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t rows, float* y, hipStream_t st,
-                     int* ctl) {
+                     int* ctl, bool dry = false) {
   if (p->n_layers < 1 || p->n_layers > 2 || p->n_head > kFusedMaxHead || plan_multi_type(p)) return 1;
   if (p->edge_masks || p->edge_dot) return 1;  // edge problems: multi-kernel path only
   if (plan_has_attention(p)) return 1;         // attention: multi-kernel path only
@@ -6626,6 +6688,7 @@ int try_rows_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t ro
     if (off + n <= cap) a.o_hw[i] = take(n);
   }
   const size_t lds = sizeof(float) * (size_t)off;
+  if (dry) return XPG_OK;
   a.n_blocks = static_cast<int>(cdiv(rows, 64));
   a.cus_per_xcd = std::max(1, device_cus() / device_xcds());
   a.ctl = ctl;
@@ -6647,6 +6710,49 @@ int try_rows_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t ro
 #undef XPG_ROWS
   return 1;
 }
+
+// The path xpg_masked_forward takes for a plan under the current environment (host only; the one
+// decision behind the launch and behind xpg_forward_describe).  kPathNone: XPG_FORWARD_STRICT=1
+// and the forced path does not take the plan (an error for both callers).  XPG_FORWARD=wide whose
+// layout declines the plan falls back like an unset XPG_FORWARD unless strict.
+enum FwdPath { kPathNone = 0, kPathWide, kPathRows, kPathFused, kPathUnfused };
+const char* const kPathName[] = {"none", "wide", "rows", "fused", "unfused"};
+
+// `go`: the launch arguments; the rows / fused kernel that takes the plan is then launched by the
+// same call that decides (one preparation of its arguments per forward), and the path reports it.
+struct FwdLaunch {
+  const uint32_t* bits;
+  float* y;
+  hipStream_t st;
+  int* ctl;
+};
+int forward_route(const xpg_forward_plan* p, int64_t rows, WideWs* W, FwdPath* path, const FwdLaunch* go = nullptr) {
+  if (wide_wanted(p) && wide_layout(p, rows, W) == 0) {
+    *path = kPathWide;
+    return XPG_OK;
+  }
+  // XPG_FORWARD_STRICT=1 (tests): a forced path that does not take the plan is an error
+  // instead of a fall-back to another path
+  const char* strict_env = getenv("XPG_FORWARD_STRICT");
+  const bool multi = forward_is("unfused");
+  const bool strict = forward_is(nullptr) && !multi && strict_env && std::strcmp(strict_env, "1") == 0;
+  *path = kPathNone;
+  if (strict && forward_is("wide")) return XPG_OK;
+  if (forward_is("fused")) {
+    const int rc = go ? try_fused_forward(p, go->bits, rows, go->y, go->st)
+                      : try_fused_forward(p, nullptr, rows, nullptr, nullptr, true);
+    if (rc == XPG_OK) *path = kPathFused;
+    if (rc != 1) return rc;
+  } else if (!multi) {
+    const int rc = go ? try_rows_forward(p, go->bits, rows, go->y, go->st, go->ctl)
+                      : try_rows_forward(p, nullptr, rows, nullptr, nullptr, nullptr, true);
+    if (rc == XPG_OK) *path = kPathRows;
+    if (rc != 1) return rc;
+  }
+  if (!strict) *path = kPathUnfused;
+  return XPG_OK;
+}
+const char* const kStrictMsg = "masked_forward: the forced XPG_FORWARD path does not take this plan";
 
 int launch_shapley(uint64_t seed, int64_t row_offset, int64_t rows, int64_t cols, uint32_t* bits, int32_t* counts,
                    hipStream_t st, const uint64_t* seed_dev = nullptr) {
@@ -7019,6 +7125,41 @@ int xpg_forward_workspace(const xpg_forward_plan* plan, int64_t rows, size_t* by
   return XPG_OK;
 }
 
+int xpg_forward_describe(const xpg_forward_plan* p, int64_t rows, char* buf, size_t n) {
+  XPG_REQ(buf != nullptr && n > 0, "forward_describe: no buffer");
+  buf[0] = 0;
+  WsLayout L;
+  int rc = layout_ws(p, rows, &L);
+  if (rc) return rc;
+  XPG_REQ(p->n_rel >= 1 && p->n0 >= 1 && p->cols > 0, "masked_forward: bad plan sizes");
+  WideWs W;
+  FwdPath path;
+  rc = forward_route(p, rows, &W, &path);
+  if (rc) return rc;
+  if (path == kPathNone) return fail(XPG_EINVAL, kStrictMsg);
+  std::string s = kPathName[path];
+  if (path == kPathWide) {
+    WidePick pick;
+    rc = wide_select(p, W, &pick);
+    if (rc) return rc;
+    s += std::string(" l1=") + pick.k1->name + " l2=" + pick.k2->name;
+  }
+  if (s.size() + 1 > n) return fail(XPG_ENOSPC, "forward_describe: buffer too small");
+  std::memcpy(buf, s.c_str(), s.size() + 1);
+  return XPG_OK;
+}
+
+int xpg_wide_variants(char* buf, size_t n) {
+  XPG_REQ(buf != nullptr && n > 0, "wide_variants: no buffer");
+  buf[0] = 0;
+  std::string s;
+  for (const WideVariant& v : kWideL1) s += std::string("l1=") + v.name + "\n";
+  for (const WideVariant& v : kWideL2) s += std::string("l2=") + v.name + "\n";
+  if (s.size() + 1 > n) return fail(XPG_ENOSPC, "wide_variants: buffer too small");
+  std::memcpy(buf, s.c_str(), s.size() + 1);
+  return XPG_OK;
+}
+
 int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t rows, float* y,
                        void* workspace, size_t workspace_bytes, xpg_stream_t stream) {
   WsLayout L;
@@ -7026,32 +7167,23 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
   if (rc) return rc;
   XPG_REQ(p->n_rel >= 1 && p->n0 >= 1 && p->cols > 0, "masked_forward: bad plan sizes");
   hipStream_t st = S(stream);
-  {
-    WideWs W;
-    if (wide_wanted(p) && wide_layout(p, rows, &W) == 0) {
-      XPG_REQ(workspace_bytes >= W.total, "masked_forward: workspace too small");
-      if (rows == 0) return XPG_OK;
-      return run_wide_forward(p, W, bits, rows, y, static_cast<char*>(workspace), st);
-    }
+  WideWs W;
+  FwdPath path;
+  // the rows / fused kernels launch from the routing call itself once the non-wide preconditions
+  // hold (a wide plan returns before `go` is read; its workspace is checked below)
+  const bool ready = workspace_bytes >= L.total && rows != 0;
+  const FwdLaunch go{bits, y, st, workspace ? reinterpret_cast<int*>(static_cast<char*>(workspace) + L.ctl) : nullptr};
+  rc = forward_route(p, rows, &W, &path, ready ? &go : nullptr);
+  if (rc) return rc;
+  if (path == kPathWide) {
+    XPG_REQ(workspace_bytes >= W.total, "masked_forward: workspace too small");
+    if (rows == 0) return XPG_OK;
+    return run_wide_forward(p, W, bits, rows, y, static_cast<char*>(workspace), st);
   }
   XPG_REQ(workspace_bytes >= L.total, "masked_forward: workspace too small");
   if (rows == 0) return XPG_OK;
-  {
-    // XPG_FORWARD_STRICT=1 (tests): a forced path that does not take the plan is an error
-    // instead of a fall-back to the multi-kernel path
-    const char* strict_env = getenv("XPG_FORWARD_STRICT");
-    const bool multi = forward_is("unfused");
-    const bool strict = forward_is(nullptr) && !multi && strict_env && std::strcmp(strict_env, "1") == 0;
-    const bool wave_rows = forward_is("fused");
-    if (wave_rows) {
-      rc = try_fused_forward(p, bits, rows, y, st);
-      if (rc != 1) return rc;
-    } else if (!multi) {
-      rc = try_rows_forward(p, bits, rows, y, st, reinterpret_cast<int*>(static_cast<char*>(workspace) + L.ctl));
-      if (rc != 1) return rc;
-    }
-    if (strict) return fail(XPG_EINVAL, "masked_forward: the forced XPG_FORWARD path does not take this plan");
-  }
+  if (path == kPathNone) return fail(XPG_EINVAL, kStrictMsg);
+  if (path == kPathFused || path == kPathRows) return XPG_OK;  // launched by forward_route
   char* ws = static_cast<char*>(workspace);
   float* kin = reinterpret_cast<float*>(ws + L.kin);
   const int words = words_of(p->cols);

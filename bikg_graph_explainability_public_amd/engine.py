@@ -490,6 +490,14 @@ def profile_read():
     return {k: (ms[i], cnt[i]) for i, k in enumerate(PROF_SLOTS)}
 
 
+def wide_variants():
+    """Every "l1=<kernel>" / "l2=<kernel>" token ForwardPlan.describe can report for the wide
+    path (xpg_wide_variants: the table the library's selection picks from)."""
+    buf = ctypes.create_string_buffer(4096)
+    _lib.check(_lib.load().xpg_wide_variants(buf, len(buf)))
+    return buf.value.decode().split()
+
+
 # ----------------------------------------------------------------------------- forward plan
 def plan_arrays(S, rel_np, queries, L, rel_eid=None):
     """Receptive-field frontiers and CSR arrays of a ForwardPlan, built on the host by the
@@ -920,6 +928,15 @@ class ForwardPlan:
         n = ctypes.c_size_t(0)
         _lib.check(_lib.load().xpg_forward_workspace(ctypes.byref(self.desc), rows, ctypes.byref(n)))
         return n.value
+
+    def describe(self, rows):
+        """The path forward() takes for `rows` mask rows under the current environment: "rows",
+        "fused", "unfused", or "wide l1=<kernel> l2=<kernel>" with the kernels' template
+        arguments.  A host query of the library's own dispatch (nothing is launched); raises
+        where forward() would refuse the plan (XPG_FORWARD_STRICT=1)."""
+        buf = ctypes.create_string_buffer(256)
+        _lib.check(_lib.load().xpg_forward_describe(ctypes.byref(self.desc), rows, buf, len(buf)))
+        return buf.value.decode()
 
     def forward(self, bits: torch.Tensor, max_ws_bytes=8 << 30, out: torch.Tensor = None,
                 workspace: torch.Tensor = None) -> torch.Tensor:

@@ -33,6 +33,8 @@
  *                                        HeteroConv-sum conv stacks with a dense head; with edge_masks set, the
  *                                        edge problem's Data.perturb_edge (data.py:500-554: mask
  *                                        columns are edges) and a dot-product link decoder
+ *   xpg_forward_describe / xpg_wide_variants — none: host queries of xpg_masked_forward's own
+ *                                        dispatch (path and wide-path kernels), for tests and logs
  *   xpg_dense                          — the dense feature x weight contraction inside each layer
  *                                        (PyG Linear / GCNConv.lin / SAGEConv.lin_l|lin_r)
  *   xpg_wlm_fit                        — train_model's epoch loop     wlm.py:132-278 with
@@ -49,7 +51,7 @@
 extern "C" {
 #endif
 
-#define XPG_ABI_VERSION 22
+#define XPG_ABI_VERSION 23
 #define XPG_MAX_TERMS 8
 
 typedef void* xpg_stream_t; /* hipStream_t */
@@ -294,6 +296,18 @@ int xpg_forward_workspace(const xpg_forward_plan* plan, int64_t rows, size_t* by
  * events are held by one call's whole enqueue sequence at a time. */
 int xpg_masked_forward(const xpg_forward_plan* plan, const uint32_t* bits, int64_t rows,
                        float* y, void* workspace, size_t workspace_bytes, xpg_stream_t stream);
+/* The dispatch decision of xpg_masked_forward(plan, rows) under the current environment, as text
+ * (v23): the path, `wide`, `rows`, `fused` or `unfused`; for `wide` also the layer-1 and layer-2
+ * kernels with their template arguments, e.g.
+ * `wide l1=k_wide_l1s<2,0> l2=k_wide_last_ws<8,32,8,1,pipe>`.  A HOST function: it launches
+ * nothing and touches no device (the launch and the query share one selection).  The plan's
+ * pointers are tested for NULL only.  Fails like xpg_masked_forward where the decision itself
+ * fails (XPG_FORWARD_STRICT=1 with a forced path that does not take the plan: XPG_EINVAL);
+ * XPG_ENOSPC when `n` bytes do not hold the text and its terminator. */
+int xpg_forward_describe(const xpg_forward_plan* plan, int64_t rows, char* buf, size_t n);
+/* Every `l1=<kernel>` / `l2=<kernel>` token xpg_forward_describe can write for the wide path, one
+ * per line (v23; the table the selection itself picks from). */
+int xpg_wide_variants(char* buf, size_t n);
 
 /* Optional per-kernel timing of xpg_masked_forward's wide (full-graph) path (v13): with profiling
  * on, every launch of a profiled kernel is bracketed by two hipEvents on its stream;

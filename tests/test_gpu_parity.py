@@ -576,6 +576,7 @@ def test_masked_forward_synthetic_archs(kind, dims, fc, fwd_path):
     rng = np.random.default_rng(5)
     m = rng.random((130, S)) < rng.random((130, 1))
     ref = oracle.masked_query_outputs(spec, x.numpy(), {None: ei.numpy()}, m, q)
+    print(f"[fwd_path] {fwd_path} -> {plan.describe(130)}")  # what this parametrisation really runs
     got = plan.forward(e.pack_masks(torch.as_tensor(m).to(DEV)))[:, 0].cpu().numpy()
     np.testing.assert_allclose(got, ref, rtol=0, atol=1e-5)
 
@@ -607,6 +608,7 @@ def test_full_graph_forward_all_targets(kind, dims, fc, fwd_path):
     m = rng.random((70, S)) < rng.random((70, 1))
     m[0] = True
     m[1] = False
+    print(f"[fwd_path] {fwd_path} -> {plan.describe(70)}")  # what this parametrisation really runs
     got = plan.forward(e.pack_masks(torch.as_tensor(m).to(DEV))).cpu().numpy()
     assert got.shape == (70, S)
     pos = plan.frontiers[-1]  # output column i is node pos[i]
