@@ -6754,24 +6754,29 @@ int forward_route(const xpg_forward_plan* p, int64_t rows, WideWs* W, FwdPath* p
 }
 const char* const kStrictMsg = "masked_forward: the forced XPG_FORWARD path does not take this plan";
 
-int launch_shapley(uint64_t seed, int64_t row_offset, int64_t rows, int64_t cols, uint32_t* bits, int32_t* counts,
-                   hipStream_t st, const uint64_t* seed_dev = nullptr) {
+// The sampler kernels by the name xpg_sampler_describe reports.  shapley_pick / comm_pick are the one
+// selection each, shared by the launch and by the query (host only: shape, environment and, for
+// the 2-D Shapley grid's default height, the device's CU count), so a test that asserts the
+// reported variant asserts the kernel that ran.
+typedef void (*ShapleyFn)(uint64_t, int64_t, int64_t, int64_t, int, uint32_t*, int32_t*, const uint64_t*);
+struct ShapleyPick {
+  ShapleyFn fn;
+  const char* name;
+  bool flat;
+  int align;
+  unsigned gx, gy;
+};
+int shapley_pick(int64_t rows, int64_t cols, ShapleyPick* p) {
   const int words = words_of(cols);
   const int quads = (words + 3) / 4;
-  if (rows == 0) return XPG_OK;
   XPG_REQ(quads <= (1 << 30), "shapley: row too long");
-  if (quads < 64) {  // short rows: lanes over (row, quad)
-    const unsigned nb = static_cast<unsigned>(std::min<int64_t>(cdiv(rows * quads, 256), 65535 * 8));
-    if (words % 4 == 0)
-      hipLaunchKernelGGL(k_shapley_flat<4>, dim3(nb), dim3(256), 0, st, seed, row_offset, rows, cols, words, bits,
-                         counts, seed_dev);
-    else if (words % 2 == 0)
-      hipLaunchKernelGGL(k_shapley_flat<2>, dim3(nb), dim3(256), 0, st, seed, row_offset, rows, cols, words, bits,
-                         counts, seed_dev);
-    else
-      hipLaunchKernelGGL(k_shapley_flat<1>, dim3(nb), dim3(256), 0, st, seed, row_offset, rows, cols, words, bits,
-                         counts, seed_dev);
-    XPG_LAUNCHED();
+  p->align = words % 4 == 0 ? 4 : (words % 2 == 0 ? 2 : 1);
+  p->flat = quads < 64;  // short rows: lanes over (row, quad)
+  if (p->flat) {
+    p->gx = static_cast<unsigned>(std::min<int64_t>(cdiv(rows * quads, 256), 65535 * 8));
+    p->gy = 1;
+    p->fn = p->align == 4 ? k_shapley_flat<4> : (p->align == 2 ? k_shapley_flat<2> : k_shapley_flat<1>);
+    p->name = p->align == 4 ? "k_shapley_flat<4>" : (p->align == 2 ? "k_shapley_flat<2>" : "k_shapley_flat<1>");
     return XPG_OK;
   }
   // rows per block: each thread makes 16 B per row, so one row per block (25,600 x 31 blocks at
@@ -6783,14 +6788,61 @@ int launch_shapley(uint64_t seed, int64_t row_offset, int64_t rows, int64_t cols
   if (const int rc = diag_env("XPG_SHAPLEY_BLOCKS", &env_blk)) return rc;
   const int64_t nblk = env_blk != 0 ? env_blk : 64 * (int64_t)device_cus();
   const int64_t gy = nblk > 0 ? std::max<int64_t>(1, std::min<int64_t>(rows, nblk / gx)) : std::min<int64_t>(rows, 65535);
-  const dim3 grid(static_cast<unsigned>(gx), static_cast<unsigned>(std::min<int64_t>(gy, 65535)));
-  if (words % 4 == 0)
-    hipLaunchKernelGGL(k_shapley<4>, grid, dim3(256), 0, st, seed, row_offset, rows, cols, words, bits, counts, seed_dev);
-  else if (words % 2 == 0)
-    hipLaunchKernelGGL(k_shapley<2>, grid, dim3(256), 0, st, seed, row_offset, rows, cols, words, bits, counts, seed_dev);
-  else
-    hipLaunchKernelGGL(k_shapley<1>, grid, dim3(256), 0, st, seed, row_offset, rows, cols, words, bits, counts, seed_dev);
+  p->gx = static_cast<unsigned>(gx);
+  p->gy = static_cast<unsigned>(std::min<int64_t>(gy, 65535));
+  p->fn = p->align == 4 ? k_shapley<4> : (p->align == 2 ? k_shapley<2> : k_shapley<1>);
+  p->name = p->align == 4 ? "k_shapley<4>" : (p->align == 2 ? "k_shapley<2>" : "k_shapley<1>");
+  return XPG_OK;
+}
+
+int launch_shapley(uint64_t seed, int64_t row_offset, int64_t rows, int64_t cols, uint32_t* bits, int32_t* counts,
+                   hipStream_t st, const uint64_t* seed_dev = nullptr) {
+  if (rows == 0) return XPG_OK;
+  ShapleyPick pick;
+  if (const int rc = shapley_pick(rows, cols, &pick)) return rc;
+  hipLaunchKernelGGL(pick.fn, dim3(pick.gx, pick.gy), dim3(256), 0, st, seed, row_offset, rows, cols, words_of(cols),
+                     bits, counts, seed_dev);
   XPG_LAUNCHED();
+  return XPG_OK;
+}
+
+typedef void (*CommFn)(uint64_t, int64_t, int64_t, int64_t, int, int, const int32_t*, int, uint32_t, int, int,
+                       const int32_t*, const int32_t*, uint32_t*, int32_t*);
+struct CommPick {
+  CommFn fn;
+  const char* name;  // k_communities<SMALL,STAGED,CM>
+  bool small, staged, cmode;
+  size_t lds;
+  unsigned grid;
+};
+const char* const kCommShapeMsg = "communities: bad shape";
+int comm_pick(int64_t rows, int64_t cols, int32_t n_comm, int32_t n_blocks, CommPick* p) {
+  XPG_REQ(cols > 0 && rows >= 0 && n_comm > 0 && n_comm <= 32 * kCommMaxWords && n_blocks > 0 && n_blocks <= n_comm,
+          kCommShapeMsg);
+  const bool small = n_comm <= 64;
+  const size_t flag_bytes = small ? 0 : sizeof(uint32_t) * 4 * static_cast<size_t>((n_comm + 31) / 32);
+  const size_t stage_bytes = sizeof(int32_t) * 5 * static_cast<size_t>(n_blocks) + sizeof(int16_t) * static_cast<size_t>(cols);
+  const bool staged = cols <= kCommStageCols && flag_bytes + stage_bytes <= 64 * 1024;
+  // XPG_COMM_PERCOL=1 (diagnostics): the per-column lookup, which the parity suite compares bitwise
+  int percol = 0;
+  if (const int rc = diag_env("XPG_COMM_PERCOL", &percol)) return rc;
+  const size_t cm_bytes = sizeof(int32_t) * (5 * static_cast<size_t>(n_blocks) + static_cast<size_t>(n_comm) * words_of(cols));
+  const bool cmode = small && cols <= kCommStageCols && cm_bytes <= 48 * 1024 && !percol;
+  p->small = small;
+  p->staged = staged || cmode;
+  p->cmode = cmode;
+  p->lds = cmode ? cm_bytes : flag_bytes + (staged ? stage_bytes : 0);
+  p->grid = static_cast<unsigned>(std::min<int64_t>(cdiv(rows, 4), staged ? 2048 : 65536));
+  if (cmode) {
+    p->fn = k_communities<true, true, true>;
+    p->name = "k_communities<1,1,1>";
+  } else if (small) {
+    p->fn = staged ? k_communities<true, true> : k_communities<true, false>;
+    p->name = staged ? "k_communities<1,1,0>" : "k_communities<1,0,0>";
+  } else {
+    p->fn = staged ? k_communities<false, true> : k_communities<false, false>;
+    p->name = staged ? "k_communities<0,1,0>" : "k_communities<0,0,0>";
+  }
   return XPG_OK;
 }
 
@@ -6995,35 +7047,36 @@ int xpg_sample_communities_rows(uint64_t seed, int64_t row_offset, int64_t rows,
   int nb = 1;  // bit length of src_rows - 1
   while ((int64_t(1) << nb) < src_rows) ++nb;
   const int hb = (nb + 1) / 2;
-  const bool small = n_comm <= 64;
-  const size_t flag_bytes = small ? 0 : sizeof(uint32_t) * 4 * static_cast<size_t>((n_comm + 31) / 32);
-  const size_t stage_bytes = sizeof(int32_t) * 5 * static_cast<size_t>(n_blocks) + sizeof(int16_t) * static_cast<size_t>(cols);
-  const bool staged = cols <= kCommStageCols && flag_bytes + stage_bytes <= 64 * 1024;
-  // XPG_COMM_PERCOL=1 (diagnostics): the per-column lookup, which the parity suite compares bitwise
-  int percol = 0;
-  if (const int rc = diag_env("XPG_COMM_PERCOL", &percol)) return rc;
-  const bool cmode = small && cols <= kCommStageCols && sizeof(int32_t) * (5 * static_cast<size_t>(n_blocks) +
-                     static_cast<size_t>(n_comm) * words_of(cols)) <= 48 * 1024 && !percol;
-  const size_t lds = cmode ? sizeof(int32_t) * (5 * static_cast<size_t>(n_blocks) + static_cast<size_t>(n_comm) * words_of(cols))
-                           : flag_bytes + (staged ? stage_bytes : 0);
-  const int64_t cap = staged ? 2048 : 65536;
-  const int64_t want = std::min<int64_t>(cdiv(rows, 4), cap);
-  const dim3 g(static_cast<unsigned>(want));
-#define XPG_COMM(SM, ST)                                                                                      \
-  hipLaunchKernelGGL((k_communities<SM, ST>), g, dim3(256), lds, S(stream), seed, row_offset, rows, cols, words_of(cols), n_comm, \
-                     blocks, n_blocks, static_cast<uint32_t>(src_rows), hb, shuffle ? 1 : 0, col_ptr, col_comm, bits, \
-                     prow)
-  if (cmode) {
-    hipLaunchKernelGGL((k_communities<true, true, true>), g, dim3(256), lds, S(stream), seed, row_offset, rows, cols,
-                       words_of(cols), n_comm, blocks, n_blocks, static_cast<uint32_t>(src_rows), hb, shuffle ? 1 : 0,
-                       col_ptr, col_comm, bits, prow);
-  } else if (small) {
-    if (staged) XPG_COMM(true, true); else XPG_COMM(true, false);
-  } else {
-    if (staged) XPG_COMM(false, true); else XPG_COMM(false, false);
-  }
-#undef XPG_COMM
+  CommPick pick;
+  if (const int rc = comm_pick(rows, cols, n_comm, n_blocks, &pick)) return rc;
+  hipLaunchKernelGGL(pick.fn, dim3(pick.grid), dim3(256), pick.lds, S(stream), seed, row_offset, rows, cols,
+                     words_of(cols), n_comm, blocks, n_blocks, static_cast<uint32_t>(src_rows), hb, shuffle ? 1 : 0,
+                     col_ptr, col_comm, bits, prow);
   XPG_LAUNCHED();
+  return XPG_OK;
+}
+
+int xpg_sampler_describe(int32_t kind, int64_t rows, int64_t cols, int32_t n_comm, int32_t n_blocks, char* buf,
+                         size_t n) {
+  XPG_REQ(buf != nullptr && n > 0, "sampler_describe: no buffer");
+  buf[0] = 0;
+  std::string s;
+  if (kind == XPG_SAMPLER_SHAPLEY) {
+    XPG_REQ(rows >= 0 && cols > 0, "shapley: bad shape");
+    ShapleyPick pick;
+    if (const int rc = shapley_pick(rows, cols, &pick)) return rc;
+    s = rows == 0 ? std::string("none")
+                  : std::string(pick.name) + " grid=" + std::to_string(pick.gx) + "x" + std::to_string(pick.gy);
+  } else if (kind == XPG_SAMPLER_COMMUNITIES) {
+    CommPick pick;
+    if (const int rc = comm_pick(rows, cols, n_comm, n_blocks, &pick)) return rc;
+    s = rows == 0 ? std::string("none")
+                  : std::string(pick.name) + " grid=" + std::to_string(pick.grid) + " lds=" + std::to_string(pick.lds);
+  } else {
+    return fail(XPG_EINVAL, "sampler_describe: unknown sampler kind");
+  }
+  if (s.size() + 1 > n) return fail(XPG_ENOSPC, "sampler_describe: buffer too small");
+  std::memcpy(buf, s.c_str(), s.size() + 1);
   return XPG_OK;
 }
 

@@ -158,6 +158,20 @@ def sample_shapley_sets(seeds, rows: int, cols: int, device):
     return bits
 
 
+SAMPLER_SHAPLEY, SAMPLER_COMMUNITIES = 0, 1
+
+
+def sampler_describe(kind: int, rows: int, cols: int, n_comm: int = 0, n_blocks: int = 0) -> str:
+    """The kernel a device sampler launches for a shape under the current XPG_* switches
+    (xpg_sampler_describe, a host query; the launchers make the same selection):
+    `k_shapley_flat<ALIGN> grid=NBx1` / `k_shapley<ALIGN> grid=GXxGY` for kind = SAMPLER_SHAPLEY
+    (`sample_shapley*`), `k_communities<SMALL,STAGED,CM> grid=NB lds=BYTES` for kind =
+    SAMPLER_COMMUNITIES (`sample_communities` of n_comm communities in n_blocks plan blocks)."""
+    buf = ctypes.create_string_buffer(128)
+    _lib.check(_lib.load().xpg_sampler_describe(kind, rows, cols, n_comm, n_blocks, buf, len(buf)))
+    return buf.value.decode()
+
+
 # torch.get_rng_state() of the CPU generator (at::CPUGeneratorImplState, legacy POD first):
 # uint64 the_initial_seed | int32 left | int32 seeded | uint64 next | uint64 state[624] | ...
 _RNG_LEFT, _RNG_NEXT, _RNG_STATE = 8, 16, 24

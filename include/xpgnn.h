@@ -35,6 +35,9 @@
  *                                        columns are edges) and a dot-product link decoder
  *   xpg_forward_describe / xpg_wide_variants — none: host queries of xpg_masked_forward's own
  *                                        dispatch (path and wide-path kernels), for tests and logs
+ *   xpg_sampler_describe               — none: host query of the device samplers' own dispatch (which
+ *                                        k_shapley / k_shapley_flat / k_communities instantiation
+ *                                        a shape launches, and its grid), for tests and logs
  *   xpg_dense                          — the dense feature x weight contraction inside each layer
  *                                        (PyG Linear / GCNConv.lin / SAGEConv.lin_l|lin_r)
  *   xpg_wlm_fit                        — train_model's epoch loop     wlm.py:132-278 with
@@ -51,7 +54,7 @@
 extern "C" {
 #endif
 
-#define XPG_ABI_VERSION 23
+#define XPG_ABI_VERSION 24
 #define XPG_MAX_TERMS 8
 
 typedef void* xpg_stream_t; /* hipStream_t */
@@ -158,6 +161,24 @@ int xpg_sample_communities_rows(uint64_t seed, int64_t row_offset, int64_t rows,
                                 int64_t src_rows, int32_t shuffle, const int32_t* col_ptr,
                                 const int32_t* col_comm, uint32_t* bits, int32_t* prow,
                                 xpg_stream_t stream);
+
+/* The dispatch decision of the device samplers under the current environment, as text (v24).  A
+ * HOST function: it launches nothing (the launchers and the query share one selection).
+ * kind = XPG_SAMPLER_SHAPLEY: the kernel xpg_sample_shapley* (rows, cols) launches and its grid,
+ * `k_shapley_flat<ALIGN> grid=NBx1` for rows of fewer than 64 quads (a quad = 4 mask words; cols
+ * <= 8064) or `k_shapley<ALIGN> grid=GXxGY` (GX = ceil(quads / 256) blocks along a row, GY blocks
+ * striding over the rows: 64 blocks per CU of the current device, 1 CU where none is visible, or
+ * XPG_SHAPLEY_BLOCKS); ALIGN = 4 / 2 / 1 by words % 4 == 0 / words % 2 == 0 / else; n_comm and
+ * n_blocks are ignored.  kind = XPG_SAMPLER_COMMUNITIES: the kernel xpg_sample_communities_rows
+ * (rows, cols, n_comm, n_blocks) launches, `k_communities<SMALL,STAGED,CM> grid=NB lds=BYTES`
+ * with SMALL = n_comm <= 64 (flags in a register, else an LDS bitset), STAGED = the columns'
+ * communities staged in LDS (cols <= 16384 and they fit), CM = one column bitmask per community
+ * in LDS (SMALL, cols <= 16384, masks + plan <= 48 KB, no XPG_COMM_PERCOL).  rows = 0: `none`.
+ * XPG_SHAPLEY_BLOCKS / XPG_COMM_PERCOL count only with XPG_DIAGNOSTICS=1, as in the launchers
+ * (XPG_EINVAL without it); XPG_ENOSPC when `n` bytes do not hold the text and its terminator. */
+enum xpg_sampler { XPG_SAMPLER_SHAPLEY = 0, XPG_SAMPLER_COMMUNITIES = 1 };
+int xpg_sampler_describe(int32_t kind, int64_t rows, int64_t cols, int32_t n_comm, int32_t n_blocks,
+                         char* buf, size_t n);
 
 /* ---------------------------------------------------------------- perturbation */
 /* keep[b*n_edges + e] = bit(b, src[e]) & bit(b, dst[e])   (data.py:420-449) */

@@ -11,6 +11,8 @@ import torch
 
 import oracle
 from golden_utils import CASES, GOLDEN, load_case, oracle_spec, repeat_masks, state_dict
+from sampler_checks import (check_community_shuffle, check_community_structure, check_dead_rows,
+                            community_case, unpack)
 
 pytestmark = pytest.mark.gpu
 
@@ -159,16 +161,7 @@ def test_shapley_sampler_device_seed_and_graph_replay():
 
 
 def _community_case(S, lens, samples, seed=0):
-    from bikg_graph_explainability_public_amd.masks import Mask
-    rng = np.random.default_rng(seed)
-    perm = rng.permutation(S)
-    pathways, o = [], 0
-    for n in lens:
-        pathways.append(sorted(perm[o:o + n].tolist()))
-        o += n
-    m = Mask(torch.zeros((S, 1)), torch.zeros((2, 0), dtype=torch.long), pathways,
-             {"interpret_samples": samples, "epochs": 2}, "node_prediction")
-    return pathways, m.community_plan()
+    return community_case(S, lens, samples, seed)
 
 
 @pytest.mark.parametrize("S, lens, samples", [(300, [40, 7, 2, 1, 25, 60, 3], 100),
@@ -186,40 +179,13 @@ def test_community_sampler_structure(S, lens, samples):
     pathways, plan = _community_case(S, lens, samples)
     blocks, src_rows, rows, _ = plan
     bits, prow = e.sample_communities(5, (blocks, src_rows, src_rows, False), pathways, S, DEV)
-    m = e.unpack_masks(bits, S).cpu().numpy()
+    u32 = lambda t: t.cpu().numpy().view(np.uint32)
+    np.testing.assert_array_equal(e.unpack_masks(bits, S).cpu().numpy(), unpack(u32(bits), S))
     prow = prow.cpu().numpy()
-    covered = np.zeros(S, bool)
-    for p in pathways:
-        covered[p] = True
-    assert not m[:, ~covered].any()
-    tail = bits.cpu().numpy().view(np.uint32)[:, -1] >> (S % 32) if S % 32 else 0
-    assert np.all(tail == 0)
-    P = len(pathways)
-    own_bits = []
-    for start, size, size_int, own, off in blocks.tolist():
-        blk = m[start:start + size]
-        assert (prow[start:start + size] == own).all()
-        own_bits.append(blk[:, pathways[own]])
-        others = [c for c in range(P) if c != own]
-        if not others:
-            continue
-        flags = np.stack([blk[:, pathways[c]].all(1) for c in others], 1)
-        anyon = np.stack([blk[:, pathways[c]].any(1) for c in others], 1)
-        assert np.array_equal(flags, anyon)                # whole communities switch together
-        assert not anyon[:size_int].any()                  # internal rows: own community only
-        if off != own:
-            assert not flags[size_int:, others.index(off)].any()
-        h = (size - size_int) // 2
-        keep = [i for i, c in enumerate(others) if c != off]
-        a, b = flags[size_int:size_int + h][:, keep], flags[size_int + h:size_int + 2 * h][:, keep]
-        assert np.array_equal(a, ~b)                       # antithetic pairs
-    ob = np.concatenate([x.ravel() for x in own_bits])
-    assert abs(ob.mean() - 0.5) < 0.05
+    check_community_structure(u32(bits), prow, S, pathways, blocks)
     # shuffled: a permutation of the same rows; deterministic; seed-dependent
     sb, sp = e.sample_communities(5, (blocks, src_rows, src_rows, True), pathways, S, DEV)
-    key = lambda x: sorted(map(bytes, x.cpu().numpy().view(np.uint8).reshape(x.shape[0], -1)))
-    assert key(sb) == key(bits) and not torch.equal(sb, bits)
-    assert np.array_equal(np.sort(sp.cpu().numpy()), np.sort(prow))
+    check_community_shuffle(u32(sb), sp.cpu().numpy(), u32(bits), prow)
     sb2, _ = e.sample_communities(5, (blocks, src_rows, src_rows, True), pathways, S, DEV)
     assert torch.equal(sb, sb2)
     sb3, _ = e.sample_communities(6, (blocks, src_rows, src_rows, True), pathways, S, DEV)
@@ -290,19 +256,12 @@ def test_community_sampler_dead_mask_and_overlap():
              {"interpret_samples": 2, "epochs": 1}, "node_prediction")
     blocks, src_rows, rows, _ = m.community_plan()
     assert blocks.tolist() == [[0, 2, 1, 0, 0], [2, 2, 1, 1, 1], [4, 2, 1, 2, 2]]
-    for seed in range(64):
+
+    def rows_of_seed(seed):
         bits, _ = e.sample_communities(seed, (blocks, src_rows, src_rows, False), pathways, 5, DEV)
-        mm = e.unpack_masks(bits, 5).cpu().numpy()
-        for start, size, size_int, own, off in blocks.tolist():
-            row = mm[start + 1]                            # the lone external row
-            outside = [s for s in range(5) if s not in pathways[own]]
-            on = [c for c in range(3) if c != own
-                  and all(row[s] for s in pathways[c] if s not in pathways[own])]
-            assert on, f"seed {seed}: dead external row in block {own}"
-            want = np.zeros(5, bool)
-            for c in on:
-                want[pathways[c]] = True
-            assert np.array_equal(row[outside], want[outside])
+        return e.unpack_masks(bits, 5).cpu().numpy()
+
+    check_dead_rows(rows_of_seed, pathways, blocks)
 
 
 # ------------------------------------------------------------------ KernelSHAP
