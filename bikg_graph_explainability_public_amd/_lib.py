@@ -11,11 +11,11 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libxpgnn.so")
-ABI_VERSION = 24
+ABI_VERSION = 25
 MAX_TERMS = 8
 
 ACT = {None: 0, "identity": 0, "relu": 1, "sigmoid": 2, "tanh": 3, "leaky_relu": 4, "elu": 5}
-TERM = {"gcn": 0, "mean": 1, "root": 2, "att": 3}
+TERM = {"gcn": 0, "mean": 1, "root": 2, "att": 3, "sum": 4, "max": 5}
 
 c_i32, c_i64, c_f32, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 

@@ -835,7 +835,9 @@ struct AggArgs {
   int kind[XPG_MAX_TERMS];
   int rel[XPG_MAX_TERMS];
   const float* table[XPG_MAX_TERMS];
-  const float* hprev;   // layer >= 2 source rows [rows][n_prev][width]
+  const float* hprev;   // layer >= 2 source rows [rows][n_prev][width]; raw layer 1: X[F_0] [n0][width]
+  int64_t hstride;      // floats between two mask rows' source rows: n_prev * width, or 0 (raw layer 1:
+                        // the feature rows are shared by every mask row)
   int width;            // source row width (floats, % 32 == 0)
   float* out;
   int64_t out_ld;
@@ -870,11 +872,80 @@ __device__ __forceinline__ void fma4(float4& a, float c, const float4 v) {
   a.w = fmaf(c, v.w, a.w);
 }
 
+__device__ __forceinline__ void max4(float4& a, const float4 v) {
+  a.x = fmaxf(a.x, v.x);
+  a.y = fmaxf(a.y, v.y);
+  a.z = fmaxf(a.z, v.z);
+  a.w = fmaxf(a.w, v.w);
+}
+
+// One XPG_TERM_MAX term of k_agg<false> (node masks; the rules are in xpgnn.h): s (all 0 on entry)
+// gets the element-wise maximum over the target's kept in-edges and, with self_mult > 0, its own
+// row.  The MEAN branch's structure: EB in-edges per round, their keep tests and then their rows
+// issued together.  The running value starts at -inf and `any` records that some edge took part:
+// without one s stays 0 (torch_scatter's fill for empty segments), while all-negative rows keep
+// their negative maximum.
+template <int LPS, int NV>
+__device__ __forceinline__ void agg_max_term(const AggArgs& a, const float* kb, const uint32_t* mrow,
+                                             const float* base, const float4* selfrow, int r, int t, int t0,
+                                             int sub, float4 (&s)[NV]) {
+  if (!(kb[(int64_t)r * a.kpitch + t0] >= 0.f)) return;  // target masked out: no edge
+  const int* pp = a.agg_ptr + (int64_t)r * (a.n_tgt + 1);
+  const float ninf = -__builtin_huge_valf();
+  float4 m[NV];
+  bool any = a.self_mult[(int64_t)r * a.n_tgt + t] > 0;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) m[j] = any ? selfrow[sub + j * LPS] : make_float4(ninf, ninf, ninf, ninf);
+  constexpr int EB = NV >= 4 ? 2 : NV == 2 ? 4 : 8;
+  const int e_end = pp[t + 1];
+  for (int eb = pp[t]; eb < e_end; eb += EB) {
+    bool kp[EB];
+    int up[EB], kx[EB];
+#pragma unroll
+    for (int q = 0; q < EB; ++q) up[q] = a.agg_f0[eb + q < e_end ? eb + q : eb];
+    if (mrow) {
+#pragma unroll
+      for (int q = 0; q < EB; ++q) kx[q] = a.f0_node[up[q]];
+#pragma unroll
+      for (int q = 0; q < EB; ++q) kp[q] = bit_of(mrow, kx[q]);
+    } else {
+#pragma unroll
+      for (int q = 0; q < EB; ++q) kp[q] = kb[(int64_t)r * a.kpitch + up[q]] >= 0.f;
+    }
+#pragma unroll
+    for (int q = 0; q < EB; ++q) {
+      kp[q] = kp[q] && eb + q < e_end;
+      up[q] = a.agg_src[eb + q < e_end ? eb + q : eb];
+    }
+#pragma unroll
+    for (int q = 0; q < EB; ++q) asm volatile("" ::"v"(up[q]));  // issued here, not sunk into the branches
+    float4 v[EB][NV];
+#pragma unroll
+    for (int q = 0; q < EB; ++q) {
+      const float4* src = reinterpret_cast<const float4*>(base + (int64_t)up[q] * a.width);
+#pragma unroll
+      for (int j = 0; j < NV; ++j) v[q][j] = kp[q] ? src[sub + j * LPS] : make_float4(ninf, ninf, ninf, ninf);
+    }
+#pragma unroll
+    for (int q = 0; q < EB; ++q) {
+      any = any || kp[q];
+#pragma unroll
+      for (int j = 0; j < NV; ++j) max4(m[j], v[q][j]);
+    }
+  }
+  if (any) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) s[j] = m[j];
+  }
+}
+
 // Masked aggregation for one conv layer.  Item = (mask row b, target t); LPS lanes per item,
 // each lane owns NV float4 feature chunks.  L1: sources are the shared pre-transformed F_0
 // tables (X W^T computed once per query: features are never masked, data.py:582) and the
 // epilogue applies bias + activation; otherwise sources are the previous layer's per-row
-// outputs and each term's aggregate is written to its slice of the GEMM input.
+// outputs (a raw layer 1: the raw feature rows X[F_0], shared by every mask row, hstride = 0) and
+// each term's aggregate is written to its slice of the GEMM input.  SUM is MEAN without the
+// divide; MAX (agg_max_term) runs in the aggregate-then-transform form only.
 template <bool L1, int LPS, int NV>
 __global__ __launch_bounds__(256) void k_agg(AggArgs a) {
   const int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -894,7 +965,7 @@ __global__ __launch_bounds__(256) void k_agg(AggArgs a) {
   for (int k = 0; k < a.n_terms; ++k) {
     const int kind = a.kind[k];
     const int r = a.rel[k];
-    const float* base = L1 ? a.table[k] : a.hprev + b * (int64_t)a.n_prev * a.width;
+    const float* base = L1 ? a.table[k] : a.hprev + b * a.hstride;
     const int self_pos = L1 ? t0 : tp;
     const float4* selfrow = reinterpret_cast<const float4*>(base + (int64_t)self_pos * a.width);
     float4 s[NV];
@@ -928,7 +999,9 @@ __global__ __launch_bounds__(256) void k_agg(AggArgs a) {
             }
           }
         }
-      } else {  // MEAN
+      } else if (!L1 && kind == XPG_TERM_MAX) {
+        agg_max_term<LPS, NV>(a, kb, mrow, base, selfrow, r, t, t0, sub, s);
+      } else {  // MEAN, SUM
         if (kt >= 0.f) {
           int sm = 0;
           if (brow) {
@@ -992,7 +1065,7 @@ __global__ __launch_bounds__(256) void k_agg(AggArgs a) {
               }
             }
           }
-          const float inv = 1.f / (cnt > 1.f ? cnt : 1.f);
+          const float inv = kind == XPG_TERM_SUM ? 1.f : 1.f / (cnt > 1.f ? cnt : 1.f);
 #pragma unroll
           for (int j = 0; j < NV; ++j) { s[j].x *= inv; s[j].y *= inv; s[j].z *= inv; s[j].w *= inv; }
         }
@@ -1253,7 +1326,7 @@ __device__ __forceinline__ void l1_rows_term(const AggArgs& a, int k, int t, int
         for (int j = 0; j < W / 2; ++j) s[j] = fma2(c, src[j], s[j]);
       }
     }
-  } else {  // MEAN
+  } else {  // MEAN, SUM (the mean without the divide)
     const int sm = a.self_mult[(int64_t)r * a.n_tgt + t];
     const float cnt = kt + static_cast<float>(sm);
     if (kt >= 0.f) {
@@ -1291,7 +1364,7 @@ __device__ __forceinline__ void l1_rows_term(const AggArgs& a, int k, int t, int
       }
     }
     if (kt >= 0.f) {
-      const f32x2 inv = 1.f / (cnt > 1.f ? cnt : 1.f);
+      const f32x2 inv = kind == XPG_TERM_SUM ? 1.f : 1.f / (cnt > 1.f ? cnt : 1.f);
 #pragma unroll
       for (int j = 0; j < W / 2; ++j) s[j] *= inv;
     }
@@ -1758,7 +1831,9 @@ __device__ __forceinline__ void rows_dense(const float* A, int K, const float* W
 }
 
 // Layer-1 output of F_1 target s for this wave's FS feature columns (lane = row).
-template <int FS>
+// SUMK: the plan holds SUM terms (MEAN without the divide, inv = 1); plans without one run the
+// SUMK = false instantiation, whose code has no test for the kind.
+template <int FS, bool SUMK>
 __device__ __forceinline__ void rows_h1(const RowsFwdArgs& a, const float* lds, int s, int fo, int lane,
                                         float (&h)[FS]) {
   const int* li = reinterpret_cast<const int*>(lds);
@@ -1782,7 +1857,7 @@ __device__ __forceinline__ void rows_h1(const RowsFwdArgs& a, const float* lds, 
       } else {
         const int sm = li[a.o_l1smul + r * a.n1 + s];
         const float cnt = kt + static_cast<float>(sm);
-        const float inv = 1.f / (cnt > 1.f ? cnt : 1.f);
+        const float inv = SUMK && kind == XPG_TERM_SUM ? 1.f : 1.f / (cnt > 1.f ? cnt : 1.f);
         cself = kt >= 0.f ? static_cast<float>(sm) * inv : 0.f;
         cedge_t = kt >= 0.f ? inv : 0.f;
       }
@@ -1838,7 +1913,7 @@ __device__ __forceinline__ void rows_h1(const RowsFwdArgs& a, const float* lds, 
 // takes a worker slot on its XCD (at most its free CUs: CUs per XCD minus the fit workgroups
 // registered there) or leaves, and the workers take 64-row blocks from one counter until none is
 // left, so the blocks go where CUs are free.  Every block is taken exactly once either way.
-template <int FS>
+template <int FS, bool SUMK = false>
 __global__ __launch_bounds__(1024) void k_rows_forward(const RowsFwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   int* li = reinterpret_cast<int*>(lds);
@@ -2022,7 +2097,7 @@ __global__ __launch_bounds__(1024) void k_rows_forward(const RowsFwdArgs a) {
     int cur_w;
     float h[FS];
     if (a.n_layers == 1) {
-      rows_h1<FS>(a, lds, t, fo, lane, h);
+      rows_h1<FS, SUMK>(a, lds, t, fo, lane, h);
 #pragma unroll
       for (int f = 0; f < FS; ++f) h0[(fo + f) * 64 + lane] = h[f];
       cur_w = a.f1_pad;
@@ -2052,13 +2127,13 @@ __global__ __launch_bounds__(1024) void k_rows_forward(const RowsFwdArgs a) {
           } else {
             sm = li[a.o_l2smul + r * a.n2 + t];
             const float cnt = kt + static_cast<float>(sm);
-            const float inv = 1.f / (cnt > 1.f ? cnt : 1.f);
+            const float inv = SUMK && kind == XPG_TERM_SUM ? 1.f : 1.f / (cnt > 1.f ? cnt : 1.f);
             cself = kt >= 0.f ? static_cast<float>(sm) * inv : 0.f;
             cedge_t = kt >= 0.f ? inv : 0.f;
           }
         }
         if (sm > 0) {
-          rows_h1<FS>(a, lds, tp, fo, lane, h);
+          rows_h1<FS, SUMK>(a, lds, tp, fo, lane, h);
 #pragma unroll
           for (int f = 0; f < FS; ++f) acc[f] = fmaf(cself, h[f], acc[f]);
         }
@@ -2068,7 +2143,7 @@ __global__ __launch_bounds__(1024) void k_rows_forward(const RowsFwdArgs a) {
             const int s1 = li[a.o_l2src + e], s0 = li[a.o_l2f0 + e];
             const float d = dvr[s0 * 64];
             const float c = kind == XPG_TERM_GCN ? d * cedge_t : (d > 0.f ? cedge_t : 0.f);
-            rows_h1<FS>(a, lds, s1, fo, lane, h);
+            rows_h1<FS, SUMK>(a, lds, s1, fo, lane, h);
 #pragma unroll
             for (int f = 0; f < FS; ++f) acc[f] = fmaf(c, h[f], acc[f]);
           }
@@ -5764,6 +5839,20 @@ bool plan_needs_degree(const xpg_forward_plan* p) {
       if (p->layers[l].terms[k].kind != XPG_TERM_ATT) return true;
   return p->edge_masks != 0;
 }
+// SUM / MAX terms (v25) and the raw (aggregate-then-transform) layer 1 that MAX needs there: the
+// multi-kernel path takes them all, the rows kernel SUM on table layers only, the fused and wide
+// kernels none (their term branches know ROOT, GCN and "else MEAN")
+bool plan_has_kind(const xpg_forward_plan* p, int kind) {
+  for (int l = 0; l < p->n_layers; ++l)
+    for (int k = 0; k < p->layers[l].n_terms && k < XPG_MAX_TERMS; ++k)
+      if (p->layers[l].terms[k].kind == kind) return true;
+  return false;
+}
+bool plan_raw_l1(const xpg_forward_plan* p) { return p->layers[0].weight != nullptr && p->layers[0].f_in_pad > 0; }
+bool plan_sum_max_raw(const xpg_forward_plan* p) {
+  return plan_has_kind(p, XPG_TERM_SUM) || plan_has_kind(p, XPG_TERM_MAX) || plan_raw_l1(p);
+}
+
 // GEMM-input slices of a layer >= 2 (one per term; an ATT term has one per head) and its score
 // slots (per ATT term: heads source scores, then heads destination scores)
 int layer_slices(const xpg_layer_desc& ly) {
@@ -5803,9 +5892,11 @@ int layout_ws(const xpg_forward_plan* p, int64_t rows, WsLayout* L) {
     const xpg_layer_desc& ly = p->layers[l];
     L->h[l] = off;
     off += align_up(sizeof(float) * (size_t)rows * ly.n_tgt * ly.f_out_pad);
-    if (l > 0) {
+    if (l > 0 || plan_raw_l1(p)) {  // the layer's dense input (layer 1: its raw form only)
       size_t a = sizeof(float) * (size_t)rows * ly.n_tgt * layer_slices(ly) * ly.f_in_pad;
       agg_max = a > agg_max ? a : agg_max;
+    }
+    if (l > 0) {
       size_t sc = sizeof(float) * (size_t)rows * p->layers[l - 1].n_tgt * layer_score_slots(ly);
       score_max = sc > score_max ? sc : score_max;
     }
@@ -6000,6 +6091,7 @@ int try_fused_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t r
   // opt-in (XPG_FORWARD=fused): per-row latency chains make it slower than k_rows_forward
   if (!forward_is("fused")) return 1;
   if (plan_has_attention(p)) return 1;  // attention: multi-kernel path only
+  if (plan_sum_max_raw(p)) return 1;    // SUM / MAX terms, raw layer 1: not in this kernel
   if (p->n_layers > kFusedMaxLayers || p->n_head > kFusedMaxHead || plan_multi_type(p)) return 1;
   if (p->edge_masks || p->edge_dot) return 1;  // edge problems: multi-kernel path only
   FusedArgs a;
@@ -6272,6 +6364,7 @@ int wide_side(WideSide** out) {
 bool wide_wanted(const xpg_forward_plan* p) {
   if (p->edge_masks || p->edge_dot) return false;  // edge problems: multi-kernel path only
   if (plan_has_attention(p)) return false;          // attention: multi-kernel path only
+  if (plan_sum_max_raw(p)) return false;            // SUM / MAX terms, raw layer 1: not in the wide kernels
   if (forward_is("wide")) return true;
   if (forward_is(nullptr)) return false;  // another path forced
   return p->n_layers == 2 && p->layers[0].n_tgt >= 8192;
@@ -6567,6 +6660,8 @@ int try_rows_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t ro
   if (p->n_layers < 1 || p->n_layers > 2 || p->n_head > kFusedMaxHead || plan_multi_type(p)) return 1;
   if (p->edge_masks || p->edge_dot) return 1;  // edge problems: multi-kernel path only
   if (plan_has_attention(p)) return 1;         // attention: multi-kernel path only
+  // SUM runs here (MEAN with inv = 1); MAX fits no per-edge coefficient and a raw layer 1 has no tables
+  if (plan_has_kind(p, XPG_TERM_MAX) || plan_raw_l1(p)) return 1;
   RowsFwdArgs a;
   std::memset(&a, 0, sizeof(a));
   a.rows = rows;
@@ -6699,10 +6794,16 @@ int try_rows_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t ro
                                                   (int64_t)a.n_blocks + 4 * a.cus_per_xcd));
   }
   const dim3 grid(nwg);
+  const bool sumk = plan_has_kind(p, XPG_TERM_SUM);  // SUM terms: the instantiation that knows them
 #define XPG_ROWS(F)                                                                                     \
   if (fs == F) {                                                                                        \
-    XPG_HIP(lds_limit(reinterpret_cast<const void*>(&k_rows_forward<F>)));      \
-    hipLaunchKernelGGL(k_rows_forward<F>, grid, dim3(64 * kRowsWaves), lds, st, a);                      \
+    if (sumk) {                                                                                         \
+      XPG_HIP(lds_limit(reinterpret_cast<const void*>(&k_rows_forward<F, true>)));                       \
+      hipLaunchKernelGGL((k_rows_forward<F, true>), grid, dim3(64 * kRowsWaves), lds, st, a);             \
+    } else {                                                                                            \
+      XPG_HIP(lds_limit(reinterpret_cast<const void*>(&k_rows_forward<F>)));                             \
+      hipLaunchKernelGGL(k_rows_forward<F>, grid, dim3(64 * kRowsWaves), lds, st, a);                    \
+    }                                                                                                   \
     XPG_LAUNCHED();                                                                                     \
     return XPG_OK;                                                                                      \
   }
@@ -7219,6 +7320,8 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
   int rc = layout_ws(p, rows, &L);
   if (rc) return rc;
   XPG_REQ(p->n_rel >= 1 && p->n0 >= 1 && p->cols > 0, "masked_forward: bad plan sizes");
+  XPG_REQ(!p->edge_masks || !(plan_has_kind(p, XPG_TERM_SUM) || plan_has_kind(p, XPG_TERM_MAX)),
+          "masked_forward: SUM / MAX terms do not take edge-mask plans");
   hipStream_t st = S(stream);
   WideWs W;
   FwdPath path;
@@ -7267,7 +7370,9 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
   for (int l = 0; l < p->n_layers; ++l) {
     const xpg_layer_desc& ly = p->layers[l];
     XPG_REQ(ly.n_terms >= 1 && ly.n_terms <= XPG_MAX_TERMS, "layer: 1..8 terms");
+    const bool raw = l == 0 && plan_raw_l1(p);
     if (layer_has_attention(ly)) {
+      XPG_REQ(!raw, "layer 1: attention terms do not take the raw form");
       float* hout = reinterpret_cast<float*>(ws + L.h[l]);
       if (l == 0) {
         rc = launch_att_layer(p, l, bits, rows, nullptr, nullptr, hout, st);
@@ -7324,9 +7429,31 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
       a.dst_type[k] = ly.tgt_type ? ly.terms[k].dst_type : -1;
       XPG_REQ(a.kind[k] == XPG_TERM_ROOT || (a.rel[k] >= 0 && a.rel[k] < p->n_rel), "term: bad relation");
       XPG_REQ(!ly.tgt_type || a.dst_type[k] < ly.n_types, "term: destination type out of range");
+      XPG_REQ(a.kind[k] >= XPG_TERM_GCN && a.kind[k] <= XPG_TERM_MAX, "term: unknown kind");
+      XPG_REQ(a.kind[k] != XPG_TERM_MAX || l > 0 || raw, "term: MAX at layer 1 needs the raw form (weight, f_in_pad)");
+      XPG_REQ(!raw || (ly.terms[k].table && ly.terms[k].table == ly.terms[0].table),
+              "raw layer 1: every term's table must be the one X[F_0] table");
     }
+    XPG_REQ(l > 0 || !ly.weight || ly.f_in_pad > 0, "layer 1: weight set without f_in_pad (the raw form needs both)");
     float* hout = reinterpret_cast<float*>(ws + L.h[l]);
-    if (l == 0) {
+    if (raw) {
+      // aggregate-then-transform on the raw feature rows, shared by every mask row (stride 0);
+      // sources and own rows by their F_0 positions
+      XPG_REQ(ly.f_in_pad % 32 == 0 && ly.f_in_pad <= 256, "raw layer 1: f_in_pad must be 32..256, a multiple of 32");
+      float* agg = reinterpret_cast<float*>(ws + L.agg);
+      a.hprev = ly.terms[0].table;
+      a.hstride = 0;
+      a.tgt_prev = ly.tgt_f0;
+      a.agg_src = ly.agg_f0;
+      a.width = ly.f_in_pad;
+      a.out = agg;
+      a.out_ld = (int64_t)ly.n_terms * ly.f_in_pad;
+      rc = launch_agg<false>(a, st);
+      if (rc) return rc;
+      rc = launch_dense(agg, rows * ly.n_tgt, a.out_ld, ly.weight, a.out_ld, a.out_ld, ly.bias, ly.f_out,
+                        ly.f_out_pad, ly.act, hout, ly.f_out_pad, st, ly.tgt_type, ly.n_tgt, ly.f_out_pad, nullptr);
+      if (rc) return rc;
+    } else if (l == 0) {
       a.width = ly.f_out_pad;
       a.out = hout;
       a.out_ld = ly.f_out_pad;
@@ -7340,6 +7467,7 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
       XPG_REQ(ly.f_in_pad == prev.f_out_pad, "layer: f_in_pad must equal previous f_out_pad");
       float* agg = reinterpret_cast<float*>(ws + L.agg);
       a.hprev = reinterpret_cast<const float*>(ws + L.h[l - 1]);
+      a.hstride = (int64_t)a.n_prev * ly.f_in_pad;
       a.width = ly.f_in_pad;
       a.out = agg;
       a.out_ld = (int64_t)ly.n_terms * ly.f_in_pad;

@@ -756,6 +756,8 @@ class ForwardPlan:
                 raise ValueError("a conv layer mixing attention with other terms is not supported")
             if att and self.edge_masks:
                 raise ValueError("attention terms on edge-mask plans are not supported")
+            if self.edge_masks and any(t.kind in ("sum", "max") for t in terms):
+                raise ValueError("sum / max terms on edge-mask plans are not supported")
             if nt_np is not None:
                 # every target of this layer has one node type: a relation term of another
                 # destination type adds exactly 0 to every target (HeteroConv sums per
@@ -777,7 +779,15 @@ class ForwardPlan:
             ld.f_out_pad = f_out_pad
             ld.n_tgt = n_t
             ld.n_edges = int(arr["layers"][li]["agg_src"].size)
-            ld.f_in_pad = 0 if li == 0 else prev_pad
+            # max is not linear: a first conv with a "max" term takes the raw form (aggregate the
+            # raw feature rows, then the dense product), like every deeper layer
+            raw = li == 0 and any(t.kind == "max" for t in terms)
+            if raw:
+                prev_pad = _rup(f_in0, 32)
+                if prev_pad > 256:
+                    raise ValueError("a first conv with a max term and an input wider than 256 "
+                                     "is not supported")
+            ld.f_in_pad = prev_pad if (li > 0 or raw) else 0
             nz = lambda a: a if a.size else np.zeros(1)
             self._i32(ld, "tgt_prev", np.arange(n_t))  # F_l is a prefix of F_{l-1}
             self._i32(ld, "tgt_f0", np.arange(n_t))  # F_l is a prefix of F_0 too
@@ -812,7 +822,14 @@ class ForwardPlan:
                     ld.terms[k].heads, ld.terms[k].head_ch = term.heads, term.head_ch
                     ld.terms[k].neg_slope = term.neg_slope
                     ld.terms[k].self_loops = int(term.self_loops)
-            if li == 0:
+            if raw:
+                # one zero-padded X[F_0] table shared by the terms (and by every mask row)
+                X0p = torch.zeros((n0, prev_pad), dtype=torch.float32, device=device)
+                X0p[:, :f_in0] = X0
+                self._keep.append(X0p)
+                for k in range(len(terms)):
+                    ld.terms[k].table = X0p.data_ptr()
+            if li == 0 and not raw:
                 for k, term in enumerate(terms):
                     T = dense(X0, term.weight.to(device), None, None)
                     Tp = torch.zeros((n0, f_out_pad), dtype=torch.float32, device=device)

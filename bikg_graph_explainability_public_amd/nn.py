@@ -1,8 +1,10 @@
-"""PyG-2.0.4-compatible graph layers (GCNConv, SAGEConv, GATConv, HeteroConv, Linear).
+"""PyG-2.0.4-compatible graph layers (GCNConv, SAGEConv, GraphConv, GINConv, GATConv, HeteroConv,
+Linear).
 
 PyTorch Geometric is not available on ROCm boxes here; these modules carry the same
 `state_dict` keys as torch_geometric 2.0.4 (`lin.weight` / `bias` for GCNConv, `lin_l.*` /
-`lin_r.weight` for SAGEConv, `convs.<src>__<rel>__<dst>.*` for HeteroConv, `weight` / `bias`
+`lin_r.weight` for SAGEConv, `lin_rel.*` / `lin_root.weight` for GraphConv, `nn.*` / `eps` for
+GINConv, `convs.<src>__<rel>__<dst>.*` for HeteroConv, `weight` / `bias`
 for Linear) so the reference checkpoints (test_data/*.pth.tar, tests/test_utils.py:10-83) load
 unchanged.  Their torch `forward` is the semantics the HIP engine compiles (engine.py); the
 engine recognises these classes and the real PyG classes by name and attributes.
@@ -111,15 +113,40 @@ class GCNConv(MessagePassing):
         return f"{self.in_channels}, {self.out_channels}"
 
 
+_AGGRS = {"mean": "mean", "add": "sum", "sum": "sum", "max": "max"}
+
+
+def aggregate(xs, edge_index, n, aggr):
+    """[n, F]: per target the mean / sum / max of the source rows xs[edge_index[0]] over its
+    in-edges (duplicates as separate entries), 0 for a target without edges — the scatter-based
+    aggregation of PyG 2.0.4's MessagePassing (torch_scatter fills empty segments with 0, also
+    for max, where a non-empty segment of negative rows keeps its negative maximum)."""
+    ei = edge_index.long()
+    src, dst = ei[0], ei[1]
+    kind = _AGGRS[aggr]
+    if kind == "max":
+        idx = dst.unsqueeze(1).expand(-1, xs.size(1))
+        return torch.zeros((n, xs.size(1)), dtype=xs.dtype, device=xs.device).scatter_reduce(
+            0, idx, xs[src], reduce="amax", include_self=False)
+    s = torch.zeros((n, xs.size(1)), dtype=xs.dtype, device=xs.device)
+    s.index_add_(0, dst, xs[src])
+    if kind == "sum":
+        return s
+    cnt = torch.zeros(n, dtype=xs.dtype, device=xs.device)
+    cnt.index_add_(0, dst, torch.ones(ei.size(1), dtype=xs.dtype, device=xs.device))
+    return s / cnt.clamp(min=1).unsqueeze(1)
+
+
 class SAGEConv(MessagePassing):
-    """SAGEConv(aggr='mean', root_weight=True, normalize=False): lin_l(mean_j x_j) + lin_r(x)."""
+    """SAGEConv(root_weight=True, normalize=False): lin_l(aggr_j x_j) + lin_r(x) with `aggr` in
+    mean / add (= sum) / max."""
 
     def __init__(self, in_channels, out_channels, bias=True, normalize=False, root_weight=True,
                  aggr="mean", **kwargs):
         super().__init__()
-        if normalize or not root_weight or aggr != "mean":
-            raise NotImplementedError("only SAGEConv(aggr='mean', root_weight=True, "
-                                      "normalize=False) is supported")
+        if normalize or not root_weight or aggr not in _AGGRS:
+            raise NotImplementedError("only SAGEConv(aggr in mean / add / sum / max, "
+                                      "root_weight=True, normalize=False) is supported")
         if isinstance(in_channels, int):
             in_channels = (in_channels, in_channels)
         self.in_channels, self.out_channels = in_channels, out_channels
@@ -129,16 +156,54 @@ class SAGEConv(MessagePassing):
 
     def forward(self, x, edge_index):
         xs, xd = (x, x) if isinstance(x, torch.Tensor) else x
-        ei = edge_index.long()
-        n = xd.size(0)
-        s = torch.zeros(n, xs.size(1), dtype=xs.dtype, device=xs.device)
-        s.index_add_(0, ei[1], xs[ei[0]])
-        cnt = torch.zeros(n, dtype=xs.dtype, device=xs.device)
-        cnt.index_add_(0, ei[1], torch.ones(ei.size(1), dtype=xs.dtype, device=xs.device))
-        return self.lin_l(s / cnt.clamp(min=1).unsqueeze(1)) + self.lin_r(xd)
+        return self.lin_l(aggregate(xs, edge_index, xd.size(0), self.aggr)) + self.lin_r(xd)
 
     def extra_repr(self):
         return f"{self.in_channels}, {self.out_channels}, aggr={self.aggr}"
+
+
+class GraphConv(MessagePassing):
+    """GraphConv (PyG 2.0.4, no edge_weight): lin_rel(aggr_j x_j) + lin_root(x) with `aggr` in
+    add (= sum) / mean / max; lin_rel carries the bias, lin_root has none.  Tuple inputs
+    (x_src, x_dst) for bipartite relations."""
+
+    def __init__(self, in_channels, out_channels, aggr="add", bias=True, **kwargs):
+        super().__init__()
+        if aggr not in _AGGRS:
+            raise NotImplementedError("only GraphConv(aggr in add / sum / mean / max) is supported")
+        if isinstance(in_channels, int):
+            in_channels = (in_channels, in_channels)
+        self.in_channels, self.out_channels, self.aggr = in_channels, out_channels, aggr
+        self.lin_rel = Linear(in_channels[0], out_channels, bias=bias)
+        self.lin_root = Linear(in_channels[1], out_channels, bias=False)
+
+    def forward(self, x, edge_index):
+        xs, xd = (x, x) if isinstance(x, torch.Tensor) else x
+        return self.lin_rel(aggregate(xs, edge_index, xd.size(0), self.aggr)) + self.lin_root(xd)
+
+    def extra_repr(self):
+        return f"{self.in_channels}, {self.out_channels}, aggr={self.aggr}"
+
+
+class GINConv(MessagePassing):
+    """GINConv (PyG 2.0.4): nn((1 + eps) x + sum_j x_j); `eps` is a buffer, or a parameter with
+    train_eps.  Tuple inputs (x_src, x_dst) for bipartite relations."""
+
+    def __init__(self, nn, eps=0.0, train_eps=False, **kwargs):
+        super().__init__()
+        self.nn = nn
+        self.initial_eps, self.aggr = float(eps), "add"
+        if train_eps:
+            self.eps = torch.nn.Parameter(torch.tensor([float(eps)]))
+        else:
+            self.register_buffer("eps", torch.tensor([float(eps)]))
+
+    def forward(self, x, edge_index):
+        xs, xd = (x, x) if isinstance(x, torch.Tensor) else x
+        return self.nn(aggregate(xs, edge_index, xd.size(0), "add") + (1 + self.eps) * xd)
+
+    def extra_repr(self):
+        return f"nn={self.nn}"
 
 
 class GATConv(MessagePassing):
@@ -236,7 +301,9 @@ class HeteroConv(nn.Module):
 class ConvStack(nn.Module):
     """Model family of the reference tests/notebooks (tests/test_utils.py:10-83,
     examples/toy_example-caseA.ipynb cell 9): `conv` = ModuleList[Conv, ReLU]*, `fc` =
-    ModuleList[Linear, act]* ending in Sigmoid.  `kind` in {"gcn", "sage", "gat"}; `hetero_rels`
+    ModuleList[Linear, act]* ending in Sigmoid.  `kind` in {"gcn", "sage", "gat"} or one of the
+    sum / max families "sage-add", "sage-max", "graphconv" (add), "graphconv-max" and "gin"
+    (GINConv over Sequential(Linear, ReLU, Linear)); `hetero_rels`
     wraps each conv in HeteroConv over the given edge types (single node type).  "gat":
     GATConv layers with `heads[i]` concatenated heads of dims[i + 1] channels (default all 1), so
     layer i reads dims[i] * heads[i - 1] columns and the head reads dims[-1] * heads[-1]."""
@@ -256,7 +323,17 @@ class ConvStack(nn.Module):
         else:
             if heads is not None:
                 raise ValueError("heads applies to kind='gat' only")
-            cls = GCNConv if kind == "gcn" else SAGEConv
+            makers = {
+                "gcn": GCNConv, "sage": SAGEConv,
+                "sage-add": lambda i, o: SAGEConv(i, o, aggr="add"),
+                "sage-max": lambda i, o: SAGEConv(i, o, aggr="max"),
+                "graphconv": GraphConv,
+                "graphconv-max": lambda i, o: GraphConv(i, o, aggr="max"),
+                "gin": lambda i, o: GINConv(nn.Sequential(Linear(i, o), nn.ReLU(), Linear(o, o))),
+            }
+            if kind not in makers:
+                raise ValueError(f"unknown ConvStack kind {kind!r}")
+            cls = makers[kind]
 
             def mk(f_in, f_out, i):
                 return cls(f_in, f_out)

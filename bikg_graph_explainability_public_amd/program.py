@@ -2,7 +2,8 @@
 
 The reference treats `arch` as a black box and calls `arch(feat, edge_index)` on the B-fold
 union graph (model.py:62-116).  The engine instead recognises the supported module family —
-GCNConv / SAGEConv (mean) / HeteroConv(sum) conv layers (and, with `attention=True`, GATConv),
+GCNConv / SAGEConv (mean, add, max) / GraphConv / GINConv / HeteroConv(sum) conv layers (and, with
+`attention=True`, GATConv),
 each optionally followed by an elementwise activation, then Linear layers with activations (the
 layout of tests/test_utils.py:10-83 and the notebooks) — and lowers it to:
 
@@ -33,7 +34,7 @@ class UnsupportedArch(ValueError):
 
 @dataclass
 class Term:
-    kind: str          # "gcn" | "mean" | "root" | "att"
+    kind: str          # "gcn" | "mean" | "sum" | "max" | "root" | "att"
     rel: int           # relation index (ignored for root)
     weight: torch.Tensor  # [f_out, f_in] (att: W_src, [heads * head_ch, f_in])
     dst_type: int = -1    # multi-node-type: destination node type of the relation
@@ -71,10 +72,13 @@ class ModelProgram:
     n_types: int = 1               # > 1: multi-node-type program (node-type-gated terms)
     out_type: Optional[int] = None  # multi-node-type: node type whose rows feed the head
     link_act: Optional[str] = None  # LinkModel: the program is its encoder; decoder act(<z_u, z_v>)
+    # ROOT-only conv layers that are the second Linear of a GINConv MLP: no message passing of
+    # their own (the module's hop count, count_message_passing, does not include them)
+    extra_layers: int = 0
 
     @property
     def hops(self):
-        return len(self.convs)
+        return len(self.convs) - self.extra_layers
 
 
 _ACTS = {"ReLU": "relu", "Sigmoid": "sigmoid", "Tanh": "tanh", "ELU": "elu",
@@ -98,8 +102,17 @@ def _is_gat(m):
         hasattr(m, a) for a in ("lin_src", "lin_dst", "att_src", "att_dst", "heads", "out_channels"))
 
 
+def _is_graphconv(m):
+    return type(m).__name__ == "GraphConv" and hasattr(m, "lin_rel") and hasattr(m, "lin_root")
+
+
+def _is_gin(m):
+    return type(m).__name__ == "GINConv" and hasattr(m, "nn") and hasattr(m, "eps")
+
+
 def _is_conv(m, attention=False):
-    return type(m).__name__ in ("GCNConv", "SAGEConv", "HeteroConv") or (attention and _is_gat(m))
+    return type(m).__name__ in ("GCNConv", "SAGEConv", "HeteroConv") or _is_graphconv(m) or _is_gin(m) \
+        or (attention and _is_gat(m))
 
 
 def _is_linear(m):
@@ -203,6 +216,47 @@ def _check_unmixed(terms):
         raise UnsupportedArch("a conv layer mixing GATConv with GCNConv / SAGEConv relations")
 
 
+_AGGR_KIND = {"mean": "mean", "add": "sum", "sum": "sum", "max": "max"}
+
+
+def _aggr_kind(conv, default):
+    aggr = getattr(conv, "aggr", default)
+    if not isinstance(aggr, str) or aggr not in _AGGR_KIND:
+        raise UnsupportedArch(f"{type(conv).__name__}(aggr={aggr!r})")
+    return _AGGR_KIND[aggr]
+
+
+def _lazy(lin):
+    return isinstance(getattr(lin, "weight", None), nn.parameter.UninitializedParameter)
+
+
+def _gin_terms(conv, rel):
+    """GINConv: nn((1 + eps) x + sum_j x_j).  nn = Linear(W, b): a "sum" term W, the root
+    (1 + eps) W and bias b.  nn = Sequential(Linear, act, Linear[, act]): that layer with the
+    inner activation, then (returned as `extra`) the second Linear and the trailing activation
+    (None: the one that follows the conv) for a ROOT-only layer."""
+    eps = conv.eps
+    eps = float(eps.detach().reshape(-1)[0]) if isinstance(eps, torch.Tensor) else float(eps)
+    mlp = conv.nn
+    extra = None
+    if _is_linear(mlp):
+        lin = mlp
+    else:
+        units = [m for m in mlp.children() if type(m).__name__ not in _SKIP] \
+            if type(mlp).__name__ == "Sequential" else []
+        shape = [("L" if _is_linear(m) else "A" if _act_name(m) is not None else "?") for m in units]
+        if "".join(shape) not in ("LAL", "LALA"):
+            raise UnsupportedArch("GINConv.nn other than Linear or Sequential(Linear, act, Linear[, act])")
+        lin = units[0]
+        extra = (units[2], _act_name(units[1]), _act_name(units[3]) if len(units) == 4 else None)
+    if _lazy(lin) or (extra is not None and _lazy(extra[0])):
+        raise UnsupportedArch("GINConv.nn with uninitialised (lazy) weights")
+    W = _f32(lin.weight)
+    b = _f32(lin.bias) if getattr(lin, "bias", None) is not None else None
+    root = ((1.0 + eps) * lin.weight.detach().double()).to(torch.float32)  # folded in fp64, rounded once
+    return [Term("sum", rel, W)], b, root, W.shape[1], W.shape[0], extra
+
+
 def _single_conv_terms(conv, rel, attention=False, bipartite=False):
     name = type(conv).__name__
     if attention and _is_gat(conv):
@@ -217,14 +271,28 @@ def _single_conv_terms(conv, rel, attention=False, bipartite=False):
         b = _f32(conv.bias) if getattr(conv, "bias", None) is not None else None
         return [Term("gcn", rel, W)], b, None, W.shape[1], W.shape[0]
     if name == "SAGEConv":
-        aggr = getattr(conv, "aggr", "mean")
-        if isinstance(aggr, str) and aggr != "mean" or getattr(conv, "normalize", False) \
-                or not getattr(conv, "root_weight", True) or getattr(conv, "project", False):
-            raise UnsupportedArch("SAGEConv other than aggr='mean', root_weight, no normalize")
+        if getattr(conv, "normalize", False) or not getattr(conv, "root_weight", True) \
+                or getattr(conv, "project", False):
+            raise UnsupportedArch("SAGEConv with normalize / project / root_weight=False")
+        kind = _aggr_kind(conv, "mean")
         Wl = _f32(conv.lin_l.weight)
         bl = _f32(conv.lin_l.bias) if getattr(conv.lin_l, "bias", None) is not None else None
         Wr = _f32(conv.lin_r.weight)
-        return [Term("mean", rel, Wl)], bl, Wr, Wl.shape[1], Wl.shape[0]
+        return [Term(kind, rel, Wl)], bl, Wr, Wl.shape[1], Wl.shape[0]
+    if _is_graphconv(conv):
+        if getattr(conv.lin_root, "bias", None) is not None:
+            raise UnsupportedArch("GraphConv.lin_root with bias")
+        if _lazy(conv.lin_rel) or _lazy(conv.lin_root):
+            raise UnsupportedArch("GraphConv with uninitialised (lazy) weights")
+        kind = _aggr_kind(conv, "add")
+        W = _f32(conv.lin_rel.weight)
+        b = _f32(conv.lin_rel.bias) if getattr(conv.lin_rel, "bias", None) is not None else None
+        return [Term(kind, rel, W)], b, _f32(conv.lin_root.weight), W.shape[1], W.shape[0]
+    if _is_gin(conv):
+        t, b, root, f_in, f_out, extra = _gin_terms(conv, rel)
+        if extra is not None:
+            raise UnsupportedArch("GINConv with an MLP inside HeteroConv")
+        return t, b, root, f_in, f_out
     raise UnsupportedArch(f"unsupported conv {name}")
 
 
@@ -257,13 +325,19 @@ def _conv_layer(conv, rel_index, attention=False):
     else:
         if rel_index is not None and len(rel_index) != 1:
             raise UnsupportedArch("homogeneous conv on a multi-relation graph")
-        terms, bias, root, f_in, f_out = _single_conv_terms(conv, 0, attention)
+        if _is_gin(conv):
+            terms, bias, root, f_in, f_out, extra = _gin_terms(conv, 0)
+            if extra is not None:
+                terms.append(Term("root", -1, root))
+                return terms, (torch.zeros(f_out) if bias is None else bias), f_in, f_out, extra
+        else:
+            terms, bias, root, f_in, f_out = _single_conv_terms(conv, 0, attention)
     _check_unmixed(terms)
     if root is not None:
         terms.append(Term("root", -1, root))
     if bias is None:
         bias = torch.zeros(f_out)
-    return terms, bias, f_in, f_out
+    return terms, bias, f_in, f_out, None
 
 
 def _pad_cols(w, n):
@@ -353,13 +427,27 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
         if multi:
             terms, bias, f_in, f_out, prog.out_type = _conv_layer_multi(
                 units[i], rel_index, list(node_type_names), attention)
+            extra = None
         else:
-            terms, bias, f_in, f_out = _conv_layer(units[i], rel_index, attention)
+            terms, bias, f_in, f_out, extra = _conv_layer(units[i], rel_index, attention)
         act = None
         if i + 1 < len(units) and _act_name(units[i + 1]) is not None:
             act = _act_name(units[i + 1])
             i += 1
-        prog.convs.append(ConvLayer(terms, bias, act, f_in, f_out))
+        if extra is not None:
+            # GINConv over an MLP: the conv layer ends in the MLP's inner activation; its second
+            # Linear follows as a ROOT-only layer (each target's own row), whose activation is the
+            # MLP's trailing one, else the one after the conv
+            lin2, act_in, act_out = extra
+            prog.convs.append(ConvLayer(terms, bias, act_in, f_in, f_out))
+            W2 = _f32(lin2.weight)
+            b2 = _f32(lin2.bias) if getattr(lin2, "bias", None) is not None else torch.zeros(W2.shape[0])
+            if act_out is not None and act is not None:
+                raise UnsupportedArch("two activations after a GINConv MLP")
+            prog.convs.append(ConvLayer([Term("root", -1, W2)], b2, act_out or act, W2.shape[1], W2.shape[0]))
+            prog.extra_layers += 1
+        else:
+            prog.convs.append(ConvLayer(terms, bias, act, f_in, f_out))
         i += 1
     if not prog.convs:
         raise UnsupportedArch("arch has no GCNConv/SAGEConv/HeteroConv layer first")

@@ -29,8 +29,9 @@
  *   xpg_popcount_rows + xpg_shap_kernel— Kernel.compute             kernels.py:115-174
  *   xpg_masked_forward                 — Data.perturbator + Model.infer + extract_node_edge_output
  *                                        (wlm.py:349-436 -> data.py:591-648, model.py:62-116,
- *                                        model.py:295-328) for GCNConv / SAGEConv / GATConv /
- *                                        HeteroConv-sum conv stacks with a dense head; with edge_masks set, the
+ *                                        model.py:295-328) for GCNConv / SAGEConv (mean, add, max) /
+ *                                        GraphConv / GINConv / GATConv / HeteroConv-sum conv
+ *                                        stacks with a dense head; with edge_masks set, the
  *                                        edge problem's Data.perturb_edge (data.py:500-554: mask
  *                                        columns are edges) and a dot-product link decoder
  *   xpg_forward_describe / xpg_wide_variants — none: host queries of xpg_masked_forward's own
@@ -54,7 +55,7 @@
 extern "C" {
 #endif
 
-#define XPG_ABI_VERSION 24
+#define XPG_ABI_VERSION 25
 #define XPG_MAX_TERMS 8
 
 typedef void* xpg_stream_t; /* hipStream_t */
@@ -68,7 +69,22 @@ enum xpg_act { XPG_ACT_NONE = 0, XPG_ACT_RELU = 1, XPG_ACT_SIGMOID = 2, XPG_ACT_
 enum xpg_term { XPG_TERM_GCN = 0,   /* D^-1/2 (A_r + I) D^-1/2 over relation r               */
                 XPG_TERM_MEAN = 1,  /* mean over kept in-edges of relation r (SAGE aggr)      */
                 XPG_TERM_ROOT = 2,  /* the target's own row (SAGE lin_r)                     */
-                XPG_TERM_ATT = 3    /* graph attention over relation r (GATConv, v22; below)  */ };
+                XPG_TERM_ATT = 3,   /* graph attention over relation r (GATConv, v22; below)  */
+                XPG_TERM_SUM = 4,   /* sum over kept in-edges of relation r (v25; below)      */
+                XPG_TERM_MAX = 5    /* element-wise max over kept in-edges (v25; below)       */ };
+/* SUM and MAX (v25; node masks only: a plan with edge_masks set and one of them is refused).  The
+ * edge set of target t in mask row b for relation r is MEAN's: every CSR in-edge (u -> t) with
+ * bit(b, u) & bit(b, t), duplicate edges as separate entries, plus self_mult[r][t] copies of
+ * (t -> t) iff bit(b, t).
+ * SUM: the sum of the source rows over that edge set (MEAN's numerator: a self-loop of
+ * multiplicity 2 adds the own row twice); an empty set gives 0.
+ * MAX: the element-wise maximum over that edge set: duplicates are irrelevant, the own row takes
+ * part iff self_mult > 0 and the target is kept; an empty set gives 0, not -inf (torch_scatter's
+ * fill for empty segments), while a non-empty set of all-negative rows gives its negative maximum.
+ * MAX is not linear, so a layer that holds a MAX term is aggregate-then-transform at every depth:
+ * at layer 1 it needs the raw form (xpg_layer_desc.weight below).  SUM runs on the multi-kernel
+ * and rows paths, MAX and raw layers on the multi-kernel path only; the fused and wide paths
+ * take neither kind. */
 
 int xpg_abi_version(void);
 const char* xpg_last_error(void);
@@ -215,7 +231,8 @@ int xpg_dense(const float* A, int64_t M, int64_t lda, const float* W, int64_t ld
 typedef struct xpg_term_desc {
   int32_t kind;            /* enum xpg_term                                             */
   int32_t rel;             /* relation index (degree slot); ignored for ROOT           */
-  const float* table;      /* layer 1 only: pre-transformed F_0 rows [n0][f_out_pad]   */
+  const float* table;      /* layer 1 only: pre-transformed F_0 rows [n0][f_out_pad]; a */
+                           /* raw layer 1: the raw feature rows X[F_0] [n0][f_in_pad]   */
   int32_t dst_type;        /* multi-node-type plans: the term only reaches targets of   */
                            /* this node type (HeteroConv relation destination); -1 = all */
   /* XPG_TERM_ATT only (v22): one term = one GATConv relation (PyG 2.0.4 semantics) with `heads`
@@ -245,7 +262,8 @@ typedef struct xpg_term_desc {
 typedef struct xpg_layer_desc {
   int32_t n_terms;
   int32_t act;             /* activation after the conv (enum xpg_act)                 */
-  int32_t f_in_pad;        /* width of this layer's input rows (layer >= 2), % 8 == 0   */
+  int32_t f_in_pad;        /* width of this layer's input rows (layer >= 2), % 8 == 0;  */
+                           /* layer 1: 0, or the raw form's feature width (below)       */
   int32_t f_out;           /* real output width                                        */
   int32_t f_out_pad;       /* padded output width, % 32 == 0, <= 256                   */
   int32_t n_tgt;           /* |F_l|                                                    */
@@ -261,6 +279,13 @@ typedef struct xpg_layer_desc {
   xpg_term_desc terms[XPG_MAX_TERMS];
   const float* weight;     /* layer >= 2: [f_out_pad][n_terms * f_in_pad] (ATT layers:   */
                            /* [f_out_pad][(sum of the terms' heads) * f_in_pad])         */
+  /* Raw layer 1 (v25): layers[0].weight != NULL and layers[0].f_in_pad > 0 (the first conv's
+   * input width rounded up to 32, at most 256) make layer 1 aggregate-then-transform like the
+   * deeper layers: every term's `table` is the one pointer to the zero-padded raw feature rows
+   * X[F_0] [n0][f_in_pad], shared by the terms and by all mask rows; the layer fills one f_in_pad-wide slice of a dense
+   * input per term (ROOT: the own row; MEAN / SUM / MAX / GCN: the usual aggregate of raw rows)
+   * and `weight` [f_out_pad][n_terms * f_in_pad] is applied with bias and activation.  Required
+   * by a MAX term at layer 1; no ATT terms.  weight == NULL: the table form, unchanged.       */
   const float* bias;       /* [n_types][f_out_pad], summed over relations, zero-padded */
   const int32_t* tgt_type; /* multi-node-type plans: [n_tgt] node type of each target;   */
                            /* NULL for homogeneous / single-node-type graphs             */
