@@ -11,11 +11,12 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libxpgnn.so")
-ABI_VERSION = 25
+ABI_VERSION = 26
 MAX_TERMS = 8
 
 ACT = {None: 0, "identity": 0, "relu": 1, "sigmoid": 2, "tanh": 3, "leaky_relu": 4, "elu": 5}
-TERM = {"gcn": 0, "mean": 1, "root": 2, "att": 3, "sum": 4, "max": 5}
+TERM = {"gcn": 0, "mean": 1, "root": 2, "att": 3, "sum": 4, "max": 5, "rel": 6}
+REL_NORM = {"mean": 0, "sum": 1}
 
 c_i32, c_i64, c_f32, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -32,7 +33,8 @@ class FitExchangeError(RuntimeError):
 class TermDesc(ctypes.Structure):
     _fields_ = [("kind", c_i32), ("rel", c_i32), ("table", c_vp), ("dst_type", c_i32),
                 ("heads", c_i32), ("head_ch", c_i32), ("neg_slope", c_f32), ("self_loops", c_i32),
-                ("att_src", c_vp), ("att_dst", c_vp)]
+                ("att_src", c_vp), ("att_dst", c_vp),
+                ("n_slices", c_i32), ("norm", c_i32), ("coef", c_vp)]
 
 
 class LayerDesc(ctypes.Structure):
@@ -42,7 +44,8 @@ class LayerDesc(ctypes.Structure):
                 ("agg_ptr", c_vp), ("agg_src", c_vp), ("agg_f0", c_vp), ("self_mult", c_vp),
                 ("terms", TermDesc * MAX_TERMS), ("weight", c_vp), ("bias", c_vp),
                 ("tgt_type", c_vp), ("n_types", c_i32),
-                ("agg_eid", c_vp), ("self_ptr", c_vp), ("self_eid", c_vp)]
+                ("agg_eid", c_vp), ("self_ptr", c_vp), ("self_eid", c_vp),
+                ("seg_ptr", c_vp), ("seg_rel", c_vp)]
 
 
 class HeadDesc(ctypes.Structure):

@@ -1292,6 +1292,161 @@ __global__ __launch_bounds__(256) void k_agg_att(AttArgs a) {
   }
 }
 
+// ------------------------------------------------------------------------------------ typed relations
+// XPG_TERM_REL (RGCNConv / FastRGCNConv; the rules are in xpgnn.h): one term for every relation of
+// the plan.  A kernel of its own: k_agg walks its terms with one pointer pair per (term, target),
+// which at 100 edge types is 100 pairs for a target that sees a handful of relations; here the
+// plan's per-target segment list names the relations to visit.
+struct RelArgs {
+  int64_t rows;
+  int n0, n_tgt, n_prev;
+  int width;  // source row width (floats, % 32 == 0, <= 256); lps = width / 4 lanes per item
+  int lps;
+  const int32_t* tgt_prev;
+  const int32_t* tgt_f0;
+  const int32_t* agg_ptr;
+  const int32_t* agg_src;
+  const int32_t* agg_f0;
+  const int32_t* self_mult;
+  const int32_t* seg_ptr;
+  const int32_t* seg_rel;
+  const int32_t* f0_node;
+  const uint32_t* bits;
+  int words;
+  int mean;            // 1: divide each relation's sum by its kept-entry count
+  const float* table;  // layer 1: [n_rel][n0][width]
+  const float* root;   // layer 1: the ROOT term's table [n0][width], or null (root_weight=False)
+  const float* hprev;  // layer >= 2 source rows [rows][n_prev][width]
+  const float* coef;   // layer >= 2, COEF: [n_rel][n_slices]
+  int n_slices;        // layer >= 2: slices the REL term fills
+  int n_root;          // layer >= 2: ROOT slices that follow (each the target's own row)
+  float* out;
+  int64_t out_ld;
+  const float* bias;  // layer 1 epilogue
+  int act;
+  int f_real;
+};
+
+// Relation r's aggregate at target t for the lane's float4 chunk: the MEAN branch of k_agg
+// (EB in-edges per round: their keep tests, then the kept rows, issued together before the first
+// add; the adds in edge order), with a source's keep test read from the mask row itself.  The
+// caller has found the target kept.
+template <bool L1>
+__device__ __forceinline__ float4 rel_segment(const RelArgs& a, const uint32_t* mrow, const float* base, int r,
+                                              int t, int self_pos, int sub) {
+  const int* pp = a.agg_ptr + (int64_t)r * (a.n_tgt + 1);
+  const int sm = a.self_mult[(int64_t)r * a.n_tgt + t];
+  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (sm > 0) fma4(s, static_cast<float>(sm), reinterpret_cast<const float4*>(base + (int64_t)self_pos * a.width)[sub]);
+  int cnt = sm;
+  constexpr int EB = 4;
+  const int e_end = pp[t + 1];
+  for (int eb = pp[t]; eb < e_end; eb += EB) {
+    int up[EB], kx[EB];
+    bool kp[EB];
+#pragma unroll
+    for (int q = 0; q < EB; ++q) {
+      const int e = eb + q < e_end ? eb + q : eb;
+      kx[q] = a.agg_f0[e];
+      up[q] = L1 ? kx[q] : a.agg_src[e];
+    }
+#pragma unroll
+    for (int q = 0; q < EB; ++q) kx[q] = a.f0_node[kx[q]];
+#pragma unroll
+    for (int q = 0; q < EB; ++q) kp[q] = bit_of(mrow, kx[q]) && eb + q < e_end;
+    float4 v[EB];
+#pragma unroll
+    for (int q = 0; q < EB; ++q)
+      v[q] = kp[q] ? reinterpret_cast<const float4*>(base + (int64_t)up[q] * a.width)[sub]
+                   : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int q = 0; q < EB; ++q) {
+      if (kp[q]) {
+        s.x += v[q].x; s.y += v[q].y; s.z += v[q].z; s.w += v[q].w;
+        ++cnt;
+      }
+    }
+  }
+  const float inv = a.mean ? 1.f / static_cast<float>(cnt > 1 ? cnt : 1) : 1.f;
+  s.x *= inv; s.y *= inv; s.z *= inv; s.w *= inv;
+  return s;
+}
+
+// Masked typed-relation aggregation of one conv layer.  Item = (mask row b, target t), lps lanes
+// per item, each lane owns one float4 chunk of the row.  A masked-out target visits no segment.
+// L1: relation r's rows come from table r, the ROOT table's own row is added, the epilogue is
+// k_agg<true>'s.  Otherwise every slice of the layer's dense input is written: without COEF slice r
+// = relation r's aggregate (zeros for relations the target does not see: the segment list is
+// ascending, one pass); with COEF slice s = sum_r coef[r][s] A_r, G slices at a time in
+// compile-time-indexed accumulators, the segments walked again per group of G; then the ROOT
+// slices, the target's own row.
+template <bool L1, bool COEF>
+__global__ __launch_bounds__(256) void k_agg_rel(RelArgs a) {
+  const int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t item = gid / a.lps;
+  const int sub = static_cast<int>(gid - item * a.lps);
+  if (item >= a.rows * a.n_tgt) return;
+  const int64_t b = item / a.n_tgt;
+  const int t = static_cast<int>(item - b * a.n_tgt);
+  const uint32_t* mrow = a.bits + b * a.words;
+  const int t0 = a.tgt_f0[t];
+  const int tp = a.tgt_prev[t];
+  const bool t_on = bit_of(mrow, a.f0_node[t0]);
+  const int sg0 = a.seg_ptr[t];
+  const int sg1 = t_on ? a.seg_ptr[t + 1] : sg0;
+  if (L1) {
+    float4 tot = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int sg = sg0; sg < sg1; ++sg) {
+      const int r = a.seg_rel[sg];
+      const float4 s = rel_segment<true>(a, mrow, a.table + (int64_t)r * a.n0 * a.width, r, t, t0, sub);
+      tot.x += s.x; tot.y += s.y; tot.z += s.z; tot.w += s.w;
+    }
+    if (a.root) {
+      const float4 s = reinterpret_cast<const float4*>(a.root + (int64_t)t0 * a.width)[sub];
+      tot.x += s.x; tot.y += s.y; tot.z += s.z; tot.w += s.w;
+    }
+    const int f0 = sub * 4;
+    float v[4] = {tot.x, tot.y, tot.z, tot.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[q] = (f0 + q < a.f_real) ? act_apply(v[q] + a.bias[f0 + q], a.act) : 0.f;
+    reinterpret_cast<float4*>(a.out + item * a.out_ld)[sub] = make_float4(v[0], v[1], v[2], v[3]);
+    return;
+  }
+  const float* base = a.hprev + b * (int64_t)a.n_prev * a.width;
+  float4* o = reinterpret_cast<float4*>(a.out + item * a.out_ld) + sub;
+  const int w4 = a.width / 4;
+  if (!COEF) {
+    int sg = sg0;
+    for (int r = 0; r < a.n_slices; ++r) {
+      float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (sg < sg1 && a.seg_rel[sg] == r) {
+        s = rel_segment<false>(a, mrow, base, r, t, tp, sub);
+        ++sg;
+      }
+      o[(int64_t)r * w4] = s;
+    }
+  } else {
+    constexpr int G = 8;
+    for (int g0 = 0; g0 < a.n_slices; g0 += G) {
+      float4 acc[G];
+#pragma unroll
+      for (int j = 0; j < G; ++j) acc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int sg = sg0; sg < sg1; ++sg) {
+        const int r = a.seg_rel[sg];
+        const float4 s = rel_segment<false>(a, mrow, base, r, t, tp, sub);
+        const float* cf = a.coef + (int64_t)r * a.n_slices + g0;
+#pragma unroll
+        for (int j = 0; j < G; ++j) fma4(acc[j], g0 + j < a.n_slices ? cf[j] : 0.f, s);
+      }
+#pragma unroll
+      for (int j = 0; j < G; ++j)
+        if (g0 + j < a.n_slices) o[(int64_t)(g0 + j) * w4] = acc[j];
+    }
+  }
+  const float4 own = reinterpret_cast<const float4*>(base + (int64_t)tp * a.width)[sub];
+  for (int k = 0; k < a.n_root; ++k) o[(int64_t)(a.n_slices + k) * w4] = own;
+}
+
 // One term of k_agg_l1_rows for the wave's 64 rows and W features: s (all 0 on entry) gets the
 // term's value, in k_agg<true>'s operation order.  Features are handled in pairs (f32x2: packed
 // fp32 add / fma / mul, two features per VALU instruction; each lane's operations per feature are
@@ -5832,8 +5987,21 @@ bool plan_has_attention(const xpg_forward_plan* p) {
     if (layer_has_attention(p->layers[l])) return true;
   return false;
 }
-// an all-attention plan reads no in-degrees: k_degree is not launched for it
+// typed-relation (XPG_TERM_REL, v26) layers run on the multi-kernel path only
+bool layer_has_rel(const xpg_layer_desc& ly) {
+  for (int k = 0; k < ly.n_terms && k < XPG_MAX_TERMS; ++k)
+    if (ly.terms[k].kind == XPG_TERM_REL) return true;
+  return false;
+}
+bool plan_has_rel(const xpg_forward_plan* p) {
+  for (int l = 0; l < p->n_layers; ++l)
+    if (layer_has_rel(p->layers[l])) return true;
+  return false;
+}
+// an all-attention plan reads no in-degrees: k_degree is not launched for it; nor for a REL plan
+// (every conv layer holds a REL term, rel_plan_check), whose kernel reads the mask bits itself
 bool plan_needs_degree(const xpg_forward_plan* p) {
+  if (plan_has_rel(p)) return p->edge_masks != 0;
   for (int l = 0; l < p->n_layers; ++l)
     for (int k = 0; k < p->layers[l].n_terms && k < XPG_MAX_TERMS; ++k)
       if (p->layers[l].terms[k].kind != XPG_TERM_ATT) return true;
@@ -5858,7 +6026,9 @@ bool plan_sum_max_raw(const xpg_forward_plan* p) {
 int layer_slices(const xpg_layer_desc& ly) {
   int n = 0;
   for (int k = 0; k < ly.n_terms && k < XPG_MAX_TERMS; ++k)
-    n += ly.terms[k].kind == XPG_TERM_ATT ? std::max(1, ly.terms[k].heads) : 1;
+    n += ly.terms[k].kind == XPG_TERM_ATT   ? std::max(1, ly.terms[k].heads)
+         : ly.terms[k].kind == XPG_TERM_REL ? std::max(1, ly.terms[k].n_slices)
+                                            : 1;
   return n;
 }
 int layer_score_slots(const xpg_layer_desc& ly) {
@@ -5885,8 +6055,8 @@ struct WsLayout {
 int layout_ws(const xpg_forward_plan* p, int64_t rows, WsLayout* L) {
   XPG_REQ(p && p->n_layers >= 1 && p->n_layers <= 64, "plan: 1..64 conv layers required");
   size_t off = 0;
-  L->kin = off;
-  off += align_up(sizeof(float) * (size_t)rows * p->n_rel * deg_pitch(p));
+  L->kin = off;  // REL plans read no degrees: no region (n_rel can be in the hundreds)
+  if (!plan_has_rel(p)) off += align_up(sizeof(float) * (size_t)rows * p->n_rel * deg_pitch(p));
   size_t agg_max = 0, score_max = 0;
   for (int l = 0; l < p->n_layers; ++l) {
     const xpg_layer_desc& ly = p->layers[l];
@@ -6077,6 +6247,89 @@ int launch_att_layer(const xpg_forward_plan* p, int l, const uint32_t* bits, int
   return XPG_OK;
 }
 
+// The argument rules of REL plans (xpgnn.h), checked on the host before anything is launched.
+int rel_plan_check(const xpg_forward_plan* p) {
+  if (!plan_has_rel(p)) return XPG_OK;
+  XPG_REQ(!p->edge_masks, "masked_forward: REL terms do not take edge-mask plans");
+  XPG_REQ(p->f0_node, "masked_forward: REL terms need f0_node");
+  for (int l = 0; l < p->n_layers; ++l) {
+    const xpg_layer_desc& ly = p->layers[l];
+    XPG_REQ(ly.n_terms >= 1 && ly.n_terms <= XPG_MAX_TERMS, "layer: 1..8 terms");
+    XPG_REQ(!ly.tgt_type, "REL layer: multi-node-type plans (tgt_type) are not taken");
+    int n_rel_terms = 0, n_root = 0;
+    for (int k = 0; k < ly.n_terms; ++k) {
+      const xpg_term_desc& td = ly.terms[k];
+      if (td.kind == XPG_TERM_ROOT) { ++n_root; continue; }
+      XPG_REQ(td.kind == XPG_TERM_REL, "REL layer: the other terms must be ROOT");
+      ++n_rel_terms;
+      XPG_REQ(td.norm == XPG_REL_MEAN || td.norm == XPG_REL_SUM, "REL term: unknown norm");
+      XPG_REQ(td.coef || td.n_slices == p->n_rel, "REL term: without coef n_slices must equal n_rel");
+      XPG_REQ(td.n_slices >= 1 && (l == 0 || td.n_slices <= 32), "REL term: 1..32 slices at layers >= 2");
+      XPG_REQ(l > 0 || (!td.coef && td.table), "REL term: layer 1 takes per-relation tables, no coef");
+    }
+    XPG_REQ(n_rel_terms == 1, "a plan with a REL term needs exactly one in every conv layer");
+    XPG_REQ(n_root <= 1 && (n_root == 0 || ly.terms[ly.n_terms - 1].kind == XPG_TERM_ROOT),
+            "REL layer: at most one ROOT term, after the REL term");
+    XPG_REQ(ly.seg_ptr && ly.seg_rel, "REL layer: seg_ptr / seg_rel missing");
+    XPG_REQ(l == 0 ? (!ly.weight && (n_root == 0 || ly.terms[ly.n_terms - 1].table)) : ly.weight != nullptr,
+            "REL layer: layer 1 takes the table form, deeper layers a stacked weight");
+  }
+  return XPG_OK;
+}
+
+// One typed-relation layer (rel_plan_check passed): layer 1 writes hout; a deeper layer fills the
+// layer's GEMM input (the caller's launch_dense follows).
+int launch_rel_layer(const xpg_forward_plan* p, int l, const uint32_t* bits, int64_t rows, const float* hprev,
+                     float* out, hipStream_t st) {
+  const xpg_layer_desc& ly = p->layers[l];
+  const xpg_term_desc& td = ly.terms[0];
+  RelArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.rows = rows;
+  a.n0 = p->n0;
+  a.n_tgt = ly.n_tgt;
+  a.n_prev = l == 0 ? p->n0 : p->layers[l - 1].n_tgt;
+  a.width = l == 0 ? ly.f_out_pad : ly.f_in_pad;
+  XPG_REQ(a.width % 32 == 0 && a.width > 0 && a.width <= 256, "REL layer: row width must be 32..256, a multiple of 32");
+  a.lps = a.width / 4;
+  a.tgt_prev = ly.tgt_prev;
+  a.tgt_f0 = ly.tgt_f0;
+  a.agg_ptr = ly.agg_ptr;
+  a.agg_src = ly.agg_src;
+  a.agg_f0 = ly.agg_f0;
+  a.self_mult = ly.self_mult;
+  a.seg_ptr = ly.seg_ptr;
+  a.seg_rel = ly.seg_rel;
+  a.f0_node = p->f0_node;
+  a.bits = bits;
+  a.words = words_of(p->cols);
+  a.mean = td.norm == XPG_REL_MEAN;
+  a.out = out;
+  const int64_t threads = rows * ly.n_tgt * a.lps;
+  if (threads == 0) return XPG_OK;
+  const dim3 grid(static_cast<unsigned>(cdiv(threads, 256))), block(256);
+  if (l == 0) {
+    a.table = td.table;
+    a.root = ly.n_terms > 1 ? ly.terms[1].table : nullptr;
+    a.out_ld = ly.f_out_pad;
+    a.bias = ly.bias;
+    a.act = ly.act;
+    a.f_real = ly.f_out;
+    hipLaunchKernelGGL((k_agg_rel<true, false>), grid, block, 0, st, a);
+    XPG_LAUNCHED();
+    return XPG_OK;
+  }
+  a.hprev = hprev;
+  a.coef = td.coef;
+  a.n_slices = td.n_slices;
+  a.n_root = ly.n_terms - 1;
+  a.out_ld = (int64_t)layer_slices(ly) * ly.f_in_pad;
+  if (td.coef) hipLaunchKernelGGL((k_agg_rel<false, true>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((k_agg_rel<false, false>), grid, block, 0, st, a);
+  XPG_LAUNCHED();
+  return XPG_OK;
+}
+
 // XPG_FORWARD=rows|fused|unfused|wide forces one xpg_masked_forward path (tests, A/B); unset or
 // empty: the plan picks it
 bool forward_is(const char* v) {
@@ -6091,6 +6344,7 @@ int try_fused_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t r
   // opt-in (XPG_FORWARD=fused): per-row latency chains make it slower than k_rows_forward
   if (!forward_is("fused")) return 1;
   if (plan_has_attention(p)) return 1;  // attention: multi-kernel path only
+  if (plan_has_rel(p)) return 1;        // typed relations (REL): multi-kernel path only
   if (plan_sum_max_raw(p)) return 1;    // SUM / MAX terms, raw layer 1: not in this kernel
   if (p->n_layers > kFusedMaxLayers || p->n_head > kFusedMaxHead || plan_multi_type(p)) return 1;
   if (p->edge_masks || p->edge_dot) return 1;  // edge problems: multi-kernel path only
@@ -6364,6 +6618,7 @@ int wide_side(WideSide** out) {
 bool wide_wanted(const xpg_forward_plan* p) {
   if (p->edge_masks || p->edge_dot) return false;  // edge problems: multi-kernel path only
   if (plan_has_attention(p)) return false;          // attention: multi-kernel path only
+  if (plan_has_rel(p)) return false;                // typed relations (REL): multi-kernel path only
   if (plan_sum_max_raw(p)) return false;            // SUM / MAX terms, raw layer 1: not in the wide kernels
   if (forward_is("wide")) return true;
   if (forward_is(nullptr)) return false;  // another path forced
@@ -6660,6 +6915,7 @@ int try_rows_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t ro
   if (p->n_layers < 1 || p->n_layers > 2 || p->n_head > kFusedMaxHead || plan_multi_type(p)) return 1;
   if (p->edge_masks || p->edge_dot) return 1;  // edge problems: multi-kernel path only
   if (plan_has_attention(p)) return 1;         // attention: multi-kernel path only
+  if (plan_has_rel(p)) return 1;               // typed relations (REL): multi-kernel path only
   // SUM runs here (MEAN with inv = 1); MAX fits no per-edge coefficient and a raw layer 1 has no tables
   if (plan_has_kind(p, XPG_TERM_MAX) || plan_raw_l1(p)) return 1;
   RowsFwdArgs a;
@@ -7322,6 +7578,8 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
   XPG_REQ(p->n_rel >= 1 && p->n0 >= 1 && p->cols > 0, "masked_forward: bad plan sizes");
   XPG_REQ(!p->edge_masks || !(plan_has_kind(p, XPG_TERM_SUM) || plan_has_kind(p, XPG_TERM_MAX)),
           "masked_forward: SUM / MAX terms do not take edge-mask plans");
+  rc = rel_plan_check(p);
+  if (rc) return rc;
   hipStream_t st = S(stream);
   WideWs W;
   FwdPath path;
@@ -7384,6 +7642,25 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
       float* agg = reinterpret_cast<float*>(ws + L.agg);
       rc = launch_att_layer(p, l, bits, rows, reinterpret_cast<const float*>(ws + L.h[l - 1]),
                             reinterpret_cast<float*>(ws + L.score), agg, st);
+      if (rc) return rc;
+      const int64_t K = (int64_t)layer_slices(ly) * ly.f_in_pad;
+      const bool fuse_here = fuse_out && p->n_head == 1 && l == p->n_layers - 1;
+      rc = launch_dense(agg, rows * ly.n_tgt, K, ly.weight, K, K, ly.bias, ly.f_out, ly.f_out_pad, ly.act, hout,
+                        ly.f_out_pad, st, ly.tgt_type, ly.n_tgt, ly.f_out_pad, fuse_here ? &fh : nullptr);
+      if (rc) return rc;
+      continue;
+    }
+    if (layer_has_rel(ly)) {
+      float* hout = reinterpret_cast<float*>(ws + L.h[l]);
+      if (l == 0) {
+        rc = launch_rel_layer(p, l, bits, rows, nullptr, hout, st);
+        if (rc) return rc;
+        continue;
+      }
+      const xpg_layer_desc& prev = p->layers[l - 1];
+      XPG_REQ(ly.f_in_pad == prev.f_out_pad, "layer: f_in_pad must equal previous f_out_pad");
+      float* agg = reinterpret_cast<float*>(ws + L.agg);
+      rc = launch_rel_layer(p, l, bits, rows, reinterpret_cast<const float*>(ws + L.h[l - 1]), agg, st);
       if (rc) return rc;
       const int64_t K = (int64_t)layer_slices(ly) * ly.f_in_pad;
       const bool fuse_here = fuse_out && p->n_head == 1 && l == p->n_layers - 1;

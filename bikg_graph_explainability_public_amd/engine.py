@@ -20,8 +20,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import ACT, TERM, ForwardPlanDesc, HeadDesc, LayerDesc, WlmParams, call, ptr
-from .program import fold_attention, stack_attention
+from ._lib import ACT, REL_NORM, TERM, ForwardPlanDesc, HeadDesc, LayerDesc, WlmParams, call, ptr
+from .program import fold_attention, relation_weights, stack_attention
 
 
 def _rup(x, m):
@@ -668,7 +668,38 @@ def h2d(a, device):
     return out
 
 
-_ATT_MAX_SLICES = 32  # (relation, head) slices of one attention layer's dense input
+_ATT_MAX_SLICES = 32  # (relation, head) slices of one attention layer's dense input; also the
+                      # relation / basis slices of a typed-relation ("rel") layer past the first
+_REL_TABLE_MAX_BYTES = 1 << 30  # per-relation layer-1 tables of a "rel" plan (a resource guard)
+
+
+def relation_segments(agg_ptr, self_mult, n_rel, n_tgt):
+    """Per-target relation lists of a "rel" layer from its CSR: (seg_ptr int64 [n_tgt + 1], seg_rel
+    int64 [n_seg]), target t's relations seg_rel[seg_ptr[t]:seg_ptr[t + 1]] = those with an in-edge
+    (agg_ptr [n_rel * (n_tgt + 1)], absolute offsets) or a self-loop (self_mult [n_rel * n_tgt]) at
+    t, ascending.  The kernel visits only these instead of n_rel pointer pairs per item."""
+    ptr_ = np.asarray(agg_ptr, dtype=np.int64).reshape(n_rel, n_tgt + 1)
+    has = (np.diff(ptr_, axis=1) > 0) | (np.asarray(self_mult).reshape(n_rel, n_tgt) > 0)
+    t_idx, r_idx = np.nonzero(has.T)  # row-major: by target, then relation ascending
+    seg_ptr = np.zeros(n_tgt + 1, dtype=np.int64)
+    np.cumsum(np.bincount(t_idx, minlength=n_tgt), out=seg_ptr[1:])
+    return seg_ptr, r_idx.astype(np.int64)
+
+
+def _rel_tables(X0, W, f_out_pad, device):
+    """Layer-1 tables [R][n0][f_out_pad] of a "rel" term: X0 times the stacked relation weights
+    W [R, f_out, f_in], on the dense kernel in column groups of at most 256."""
+    R, f_out, _ = W.shape
+    n0 = X0.shape[0]
+    T = torch.zeros((R, n0, f_out_pad), dtype=torch.float32, device=device)
+    per = max(1, 256 // f_out_pad)
+    for r0 in range(0, R, per):
+        n = min(per, R - r0)
+        Wg = torch.zeros((n, f_out_pad, W.shape[2]), dtype=torch.float32, device=device)
+        Wg[:, :f_out] = W[r0:r0 + n]
+        C = dense(X0, Wg.reshape(n * f_out_pad, -1), None, None)  # [n0, n * f_out_pad]
+        T[r0:r0 + n] = C.reshape(n0, n, f_out_pad).permute(1, 0, 2)
+    return T
 
 # ForwardPlan drops the relation terms of other destination types from a layer whose targets
 # share one node type (they add exactly 0); False keeps every term (the parity suite's reference)
@@ -758,6 +789,26 @@ class ForwardPlan:
                 raise ValueError("attention terms on edge-mask plans are not supported")
             if self.edge_masks and any(t.kind in ("sum", "max") for t in terms):
                 raise ValueError("sum / max terms on edge-mask plans are not supported")
+            rel = [t for t in terms if t.kind == "rel"]
+            if rel:
+                if len(rel) != 1 or terms[0] is not rel[0] or len(terms) > 2 or \
+                        any(t.kind != "root" for t in terms[1:]):
+                    raise ValueError("a typed-relation layer holds one rel term and at most one root term")
+                if self.edge_masks:
+                    raise ValueError("rel terms on edge-mask plans are not supported")
+                if program.n_types > 1:
+                    raise ValueError("rel terms on multi-node-type programs are not supported")
+                if rel[0].num_relations != self.n_rel:
+                    raise ValueError(f"conv with {rel[0].num_relations} relations on a plan of "
+                                     f"{self.n_rel} edge types")
+                if li > 0 and rel[0].slices > _ATT_MAX_SLICES:
+                    raise ValueError(f"typed-relation layer past the first with more than "
+                                     f"{_ATT_MAX_SLICES} relation / basis slices is not supported")
+                if li == 0 and self.n_rel * n0 * f_out_pad * 4 > _REL_TABLE_MAX_BYTES:
+                    raise ValueError("typed-relation layer-1 tables exceed "
+                                     f"{_REL_TABLE_MAX_BYTES >> 20} MiB")
+            elif any(any(t.kind == "rel" for t in c.terms) for c in program.convs):
+                raise ValueError("a program mixing typed-relation layers with other layers is not supported")
             if nt_np is not None:
                 # every target of this layer has one node type: a relation term of another
                 # destination type adds exactly 0 to every target (HeteroConv sums per
@@ -796,6 +847,10 @@ class ForwardPlan:
             self._i32(ld, "agg_src", nz(lay["agg_src"]))
             self._i32(ld, "agg_f0", nz(lay["agg_f0"]))
             self._i32(ld, "self_mult", lay["self_mult"])
+            if rel:
+                seg_ptr, seg_rel = relation_segments(lay["agg_ptr"], lay["self_mult"], self.n_rel, n_t)
+                self._i32(ld, "seg_ptr", seg_ptr)
+                self._i32(ld, "seg_rel", nz(seg_rel))
             if self.edge_masks:
                 self._i32(ld, "agg_eid", nz(lay["agg_eid"]))
                 self._i32(ld, "self_ptr", lay["self_ptr"])
@@ -822,6 +877,9 @@ class ForwardPlan:
                     ld.terms[k].heads, ld.terms[k].head_ch = term.heads, term.head_ch
                     ld.terms[k].neg_slope = term.neg_slope
                     ld.terms[k].self_loops = int(term.self_loops)
+                if term.kind == "rel":
+                    ld.terms[k].n_slices = self.n_rel if li == 0 else term.slices
+                    ld.terms[k].norm = REL_NORM[term.norm]
             if raw:
                 # one zero-padded X[F_0] table shared by the terms (and by every mask row)
                 X0p = torch.zeros((n0, prev_pad), dtype=torch.float32, device=device)
@@ -831,6 +889,14 @@ class ForwardPlan:
                     ld.terms[k].table = X0p.data_ptr()
             if li == 0 and not raw:
                 for k, term in enumerate(terms):
+                    if term.kind == "rel":
+                        # one table per relation (bases folded into W_r): an edge reads one row
+                        Wr = self._program_tensor(program, ("rel_l1", li, id(term)),
+                                                  lambda term=term: relation_weights(term).to(device))
+                        Tp = _rel_tables(X0, Wr, f_out_pad, device)
+                        self._keep.append(Tp)
+                        ld.terms[k].table = Tp.data_ptr()
+                        continue
                     T = dense(X0, term.weight.to(device), None, None)
                     Tp = torch.zeros((n0, f_out_pad), dtype=torch.float32, device=device)
                     Tp[:, :conv.f_out] = T
@@ -863,6 +929,27 @@ class ForwardPlan:
                 for k, (v_s, v_d) in enumerate(vecs):
                     self._keep += [v_s, v_d]
                     ld.terms[k].att_src, ld.terms[k].att_dst = v_s.data_ptr(), v_d.data_ptr()
+            elif rel:
+                # slice s of the dense input meets V_s^T / W_r^T, the root slice the root weight
+                def make_rel(conv=conv, terms=terms, prev_pad=prev_pad, f_out_pad=f_out_pad):
+                    t0 = terms[0]
+                    w = torch.zeros((f_out_pad, (t0.slices + len(terms) - 1) * prev_pad),
+                                    dtype=torch.float32, device=device)
+                    for s_ in range(t0.slices):
+                        w[:conv.f_out, s_ * prev_pad:s_ * prev_pad + conv.f_in] = t0.weight[s_].to(device)
+                    for k, term in enumerate(terms[1:]):
+                        c0 = (t0.slices + k) * prev_pad
+                        w[:conv.f_out, c0:c0 + conv.f_in] = term.weight.to(device)
+                    coef = None if t0.coef is None else \
+                        t0.coef.to(device=device, dtype=torch.float32).contiguous()
+                    return w, coef
+                Wc, coef = self._program_tensor(program, ("wc_rel", li, tuple(id(t) for t in terms)),
+                                                make_rel)
+                self._keep.append(Wc)
+                ld.weight = Wc.data_ptr()
+                if coef is not None:
+                    self._keep.append(coef)
+                    ld.terms[0].coef = coef.data_ptr()
             else:
                 def make_wc(conv=conv, terms=terms, prev_pad=prev_pad, f_out_pad=f_out_pad):
                     w = torch.zeros((f_out_pad, len(terms) * prev_pad), dtype=torch.float32,

@@ -1,11 +1,11 @@
-"""PyG-2.0.4-compatible graph layers (GCNConv, SAGEConv, GraphConv, GINConv, GATConv, HeteroConv,
-Linear).
+"""PyG-2.0.4-compatible graph layers (GCNConv, SAGEConv, GraphConv, GINConv, GATConv, RGCNConv,
+HeteroConv, Linear).
 
 PyTorch Geometric is not available on ROCm boxes here; these modules carry the same
 `state_dict` keys as torch_geometric 2.0.4 (`lin.weight` / `bias` for GCNConv, `lin_l.*` /
 `lin_r.weight` for SAGEConv, `lin_rel.*` / `lin_root.weight` for GraphConv, `nn.*` / `eps` for
-GINConv, `convs.<src>__<rel>__<dst>.*` for HeteroConv, `weight` / `bias`
-for Linear) so the reference checkpoints (test_data/*.pth.tar, tests/test_utils.py:10-83) load
+GINConv, `weight` / `comp` / `root` / `bias` for RGCNConv, `convs.<src>__<rel>__<dst>.*` for
+HeteroConv, `weight` / `bias` for Linear) so the reference checkpoints (test_data/*.pth.tar, tests/test_utils.py:10-83) load
 unchanged.  Their torch `forward` is the semantics the HIP engine compiles (engine.py); the
 engine recognises these classes and the real PyG classes by name and attributes.
 """
@@ -275,6 +275,89 @@ class GATConv(MessagePassing):
         return f"{self.in_channels}, {self.out_channels}, heads={self.heads}"
 
 
+class RGCNConv(MessagePassing):
+    """RGCNConv (PyG 2.0.4, dense features): out[t] = sum_r AGG_{e = (u -> t), type(e) = r} x_u W_r
+    + x_t root + bias, W_r [in, out] (not Linear's [out, in]).  `aggr` = mean (the default; per
+    relation over that relation's in-edges of t, a relation without in-edge adds 0) or add / sum.
+    Weight forms: plain `weight` [R, in, out]; `num_bases` = B: `weight` [B, in, out] and `comp`
+    [R, B], W_r = sum_b comp[r, b] weight[b]; `num_blocks` = nb: `weight` [R, nb, in / nb, out / nb],
+    W_r block-diagonal.  No self-loop handling: a (t -> t) edge of type r is an ordinary edge of
+    relation r.  FastRGCNConv has the same parameters and the same maths."""
+
+    def __init__(self, in_channels, out_channels, num_relations, num_bases=None, num_blocks=None,
+                 aggr="mean", root_weight=True, bias=True, **kwargs):
+        super().__init__()
+        if aggr not in ("mean", "add", "sum"):
+            raise NotImplementedError("only RGCNConv(aggr in mean / add / sum) is supported")
+        if num_bases is not None and num_blocks is not None:
+            raise ValueError("Can not apply both basis-decomposition and block-diagonal-decomposition "
+                             "at the same time.")
+        if isinstance(in_channels, int):
+            in_channels = (in_channels, in_channels)
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.in_channels_l = in_channels[0]
+        self.num_relations, self.num_bases, self.num_blocks = num_relations, num_bases, num_blocks
+        self.aggr, self.root_weight = aggr, root_weight
+        f_in = in_channels[0]
+        if num_bases is not None:
+            self.weight = nn.Parameter(torch.empty(num_bases, f_in, out_channels))
+            self.comp = nn.Parameter(torch.empty(num_relations, num_bases))
+        elif num_blocks is not None:
+            if f_in % num_blocks or out_channels % num_blocks:
+                raise ValueError("Channels must be divisible by num_blocks")
+            self.weight = nn.Parameter(torch.empty(num_relations, num_blocks, f_in // num_blocks,
+                                                   out_channels // num_blocks))
+            self.register_parameter("comp", None)
+        else:
+            self.weight = nn.Parameter(torch.empty(num_relations, f_in, out_channels))
+            self.register_parameter("comp", None)
+        if root_weight:
+            self.root = nn.Parameter(torch.empty(in_channels[1], out_channels))
+        else:
+            self.register_parameter("root", None)
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(out_channels))
+        else:
+            self.register_parameter("bias", None)
+        for p in (self.weight, self.comp, self.root):  # glorot
+            if p is not None:
+                _uniform_(p, math.sqrt(6.0 / (p.size(-2) + p.size(-1))))
+
+    def relation_weights(self):
+        """The effective dense W_r: [R, in, out]."""
+        w = self.weight
+        if self.num_bases is not None:
+            return (self.comp @ w.reshape(self.num_bases, -1)).reshape(
+                self.num_relations, w.size(1), w.size(2))
+        if self.num_blocks is not None:
+            return torch.stack([torch.block_diag(*w[r]) for r in range(self.num_relations)])
+        return w
+
+    def forward(self, x, edge_index, edge_type):
+        xs, xd = (x, x) if isinstance(x, torch.Tensor) or x is None else x
+        if xs is None or not torch.is_floating_point(xs):
+            raise NotImplementedError("featureless RGCNConv (node indices as x) is not supported")
+        ei, et = edge_index.long(), edge_type.long()
+        n = xd.size(0)
+        W = self.relation_weights()
+        out = torch.zeros((n, self.out_channels), dtype=xs.dtype, device=xs.device)
+        for r in range(self.num_relations):
+            sel = et == r
+            out = out + aggregate(xs, ei[:, sel], n, self.aggr) @ W[r]
+        if self.root is not None:
+            out = out + xd @ self.root
+        if self.bias is not None:
+            out = out + self.bias
+        return out
+
+    def extra_repr(self):
+        return f"{self.in_channels[0]}, {self.out_channels}, num_relations={self.num_relations}"
+
+
+class FastRGCNConv(RGCNConv):
+    """PyG's FastRGCNConv: RGCNConv's parameters and maths (a different evaluation order there)."""
+
+
 class HeteroConv(nn.Module):
     """HeteroConv(convs, aggr='sum'): per edge type conv, outputs summed per destination type."""
 
@@ -364,6 +447,38 @@ class ConvStack(nn.Module):
                 x = c(x)
         if isinstance(x, dict):
             x = x[list(x.keys())[0]]
+        for layer in self.fc:
+            x = layer(x)
+        return x
+
+
+class RGCNStack(nn.Module):
+    """Relational model family on a typed-edge graph, called with the reference's 4-argument
+    convention `arch(x, edge_index, node_types, edge_types)` (model.py:102-112): `conv` =
+    ModuleList[RGCNConv, ReLU]*, `fc` = ModuleList[Linear, act]* ending in Sigmoid (or Identity) —
+    the registration order program.compile_arch walks.  `node_types` is accepted and unused (one
+    node type)."""
+
+    def __init__(self, dims, fc_dims, num_relations, num_bases=None, num_blocks=None, aggr="mean",
+                 final_act="sigmoid", root_weight=True, bias=True):
+        super().__init__()
+        convs = []
+        for i in range(len(dims) - 1):
+            convs.append(RGCNConv(dims[i], dims[i + 1], num_relations, num_bases=num_bases,
+                                  num_blocks=num_blocks, aggr=aggr, root_weight=root_weight, bias=bias))
+            convs.append(nn.ReLU())
+        self.conv = nn.ModuleList(convs)
+        fcs = []
+        for i in range(len(fc_dims) - 1):
+            fcs.append(Linear(fc_dims[i], fc_dims[i + 1]))
+            last = i == len(fc_dims) - 2
+            fcs.append((nn.Sigmoid() if final_act == "sigmoid" else nn.Identity()) if last
+                       else nn.ReLU())
+        self.fc = nn.ModuleList(fcs)
+
+    def forward(self, x, edge_index, node_types, edge_types):
+        for i, c in enumerate(self.conv):
+            x = c(x, edge_index, edge_types) if i % 2 == 0 else c(x)
         for layer in self.fc:
             x = layer(x)
         return x

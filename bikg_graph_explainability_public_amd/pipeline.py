@@ -18,7 +18,7 @@ import torch
 from . import engine
 from .data import Data
 from .model import Model
-from .program import UnsupportedArch, compile_arch
+from .program import UnsupportedArch, check_rel_features, compile_arch
 
 
 # generic multi-node-type path: one arch call over the per-type disjoint union of the copies
@@ -30,6 +30,31 @@ def relation_edges(edge_index, edge_type, n_rel):
         return [edge_index]
     et = edge_type.to(edge_index.device)
     return [edge_index[:, et == r] for r in range(n_rel)]
+
+
+def typed_relations(prog):
+    """The relation count of a typed-relation (RGCNConv) program, 0 for every other program.
+    ValueError when its convs disagree."""
+    counts = {t.num_relations for c in prog.convs for t in c.terms if t.kind == "rel"}
+    if len(counts) > 1:
+        raise ValueError(f"RGCNConv layers with different num_relations {sorted(counts)}")
+    return counts.pop() if counts else 0
+
+
+def typed_relation_edges(edge_index, edge_type, n_rel):
+    """relation_edges for a typed-relation program: it needs the edge types, all inside [0, n_rel)."""
+    if edge_type is None:
+        raise ValueError("a RGCNConv model needs edge_types")
+    et = edge_type.reshape(-1)
+    if et.numel() != edge_index.shape[1]:
+        raise ValueError("edge_types must give one type per edge")
+    if et.numel() and (int(et.min()) < 0 or int(et.max()) >= n_rel):
+        raise ValueError(f"edge type outside [0, {n_rel})")
+    # one stable sort on the host (the plan builder reads host arrays) instead of n_rel device
+    # selections: each relation's edges in edge order, as relation_edges gives them
+    ei, et = edge_index.detach().cpu(), et.detach().cpu().long()
+    order = torch.argsort(et, stable=True)
+    return list(torch.split(ei[:, order], torch.bincount(et, minlength=n_rel).tolist(), dim=1))
 
 
 _PROGRAMS = collections.OrderedDict()  # compiled_program's cache: key -> (weakref(arch), program)
@@ -75,6 +100,10 @@ def build_plan(arch, feat, edge_index, queries, node_type=None, edge_type=None,
     `attention=True` (opt-in, Explainer params["attention_engine"]) also compiles GATConv
     relations, which otherwise run on the generic torch path.
 
+    A stack of RGCNConv / FastRGCNConv layers (the 4-argument call arch(x, edge_index, node_types,
+    edge_types), model.py:102-112) takes `edge_type` as its relations, with or without
+    `edge_type_names`; every other program ignores the types of a graph without names, as before.
+
     Multi-node-type graphs (model.py:118-253): the program's terms are gated by destination
     node type and the query is the reference's `out[sub_ind, 0]` — row sub_ind of the output
     node type's block — so `queries` are positions inside that type and are mapped to subgraph
@@ -87,6 +116,7 @@ def build_plan(arch, feat, edge_index, queries, node_type=None, edge_type=None,
         prog = compiled_program(arch, edge_type_names if hetero else None,
                                 node_type_names if multi else None, module_state,
                                 attention=attention)
+        check_rel_features(prog, feat)
     except UnsupportedArch as e:
         warnings.warn(f"engine cannot compile arch ({e}); using the generic torch path")
         return None
@@ -104,9 +134,14 @@ def build_plan(arch, feat, edge_index, queries, node_type=None, edge_type=None,
         queries = [int(rows_t[q]) for q in queries]
     elif hetero and padded_dims is not None and padded_dims[0] > 0:
         x = feat[:, :feat.shape[1] - padded_dims[0]]
-    rels = relation_edges(edge_index, edge_type if hetero else None,
-                          len(edge_type_names) if hetero else 1)
     try:
+        typed = typed_relations(prog)
+        if typed:
+            # RGCNConv stacks: the relations are the edge types, named or not
+            rels = typed_relation_edges(edge_index, edge_type, typed)
+        else:
+            rels = relation_edges(edge_index, edge_type if hetero else None,
+                                  len(edge_type_names) if hetero else 1)
         plan = engine.ForwardPlan(prog, x, rels, queries, node_type=nt)
     except ValueError as e:
         warnings.warn(f"engine plan rejected ({e}); using the generic torch path")

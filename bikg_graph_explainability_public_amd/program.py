@@ -2,8 +2,8 @@
 
 The reference treats `arch` as a black box and calls `arch(feat, edge_index)` on the B-fold
 union graph (model.py:62-116).  The engine instead recognises the supported module family —
-GCNConv / SAGEConv (mean, add, max) / GraphConv / GINConv / HeteroConv(sum) conv layers (and, with
-`attention=True`, GATConv),
+GCNConv / SAGEConv (mean, add, max) / GraphConv / GINConv / HeteroConv(sum) conv layers, stacks of RGCNConv / FastRGCNConv on a
+typed-edge graph (and, with `attention=True`, GATConv),
 each optionally followed by an elementwise activation, then Linear layers with activations (the
 layout of tests/test_utils.py:10-83 and the notebooks) — and lowers it to:
 
@@ -34,9 +34,9 @@ class UnsupportedArch(ValueError):
 
 @dataclass
 class Term:
-    kind: str          # "gcn" | "mean" | "sum" | "max" | "root" | "att"
-    rel: int           # relation index (ignored for root)
-    weight: torch.Tensor  # [f_out, f_in] (att: W_src, [heads * head_ch, f_in])
+    kind: str          # "gcn" | "mean" | "sum" | "max" | "root" | "att" | "rel"
+    rel: int           # relation index (ignored for root and rel)
+    weight: torch.Tensor  # [f_out, f_in] (att: W_src, [heads * head_ch, f_in]; rel: [slices, f_out, f_in])
     dst_type: int = -1    # multi-node-type: destination node type of the relation
     # kind "att" (GATConv, PyG 2.0.4): one term per relation
     heads: int = 1
@@ -46,6 +46,15 @@ class Term:
     weight_dst: Optional[torch.Tensor] = None  # bipartite relations: W_dst; None: W_src for both ends
     neg_slope: float = 0.2
     self_loops: bool = False
+    # kind "rel" (RGCNConv / FastRGCNConv, PyG 2.0.4): one term per conv layer, over every edge
+    # type of the graph.  Per relation r the mean (norm "mean": over that relation's kept in-edges,
+    # 0 without one) or sum (norm "sum") A_r of the source rows; the term adds sum_s B_s weight[s]^T
+    # with B_s = A_s (coef None: slices == num_relations, weight[r] = W_r^T, block-diagonal weights
+    # expanded) or B_s = sum_r coef[r, s] A_r (basis decomposition: weight[s] = V_s^T, coef = comp)
+    num_relations: int = 0
+    norm: str = "mean"
+    slices: int = 0
+    coef: Optional[torch.Tensor] = None        # [num_relations, slices]
 
 
 @dataclass
@@ -110,9 +119,16 @@ def _is_gin(m):
     return type(m).__name__ == "GINConv" and hasattr(m, "nn") and hasattr(m, "eps")
 
 
+_RGCN_NAMES = ("RGCNConv", "FastRGCNConv")
+
+
+def _is_rgcn(m):
+    return type(m).__name__ in _RGCN_NAMES and hasattr(m, "weight") and hasattr(m, "num_relations")
+
+
 def _is_conv(m, attention=False):
     return type(m).__name__ in ("GCNConv", "SAGEConv", "HeteroConv") or _is_graphconv(m) or _is_gin(m) \
-        or (attention and _is_gat(m))
+        or _is_rgcn(m) or (attention and _is_gat(m))
 
 
 def _is_linear(m):
@@ -257,8 +273,68 @@ def _gin_terms(conv, rel):
     return [Term("sum", rel, W)], b, root, W.shape[1], W.shape[0], extra
 
 
+_REL_NORM = {"mean": "mean", "add": "sum", "sum": "sum"}
+
+
+def _rgcn_terms(conv):
+    """RGCNConv / FastRGCNConv as one "rel" term (+ root weight and bias).  W_r is [in, out] in
+    the module; the term holds the transposes.  Folds (the block-diagonal expansion) are done in
+    fp64 and rounded once."""
+    name = type(conv).__name__
+    aggr = getattr(conv, "aggr", "mean")
+    if not isinstance(aggr, str) or aggr not in _REL_NORM:
+        raise UnsupportedArch(f"{name}(aggr={aggr!r})")
+    w = conv.weight
+    if isinstance(w, nn.parameter.UninitializedParameter) or \
+            isinstance(getattr(conv, "root", None), nn.parameter.UninitializedParameter):
+        raise UnsupportedArch(f"{name} with uninitialised (lazy) weights")
+    R = int(conv.num_relations)
+    nb, nk = getattr(conv, "num_bases", None), getattr(conv, "num_blocks", None)
+    w = w.detach().double()
+    coef = None
+    if nb is not None:
+        comp = getattr(conv, "comp", None)
+        if comp is None or w.dim() != 3 or tuple(comp.shape) != (R, w.shape[0]):
+            raise UnsupportedArch(f"{name}: comp does not match num_relations x num_bases")
+        coef = _f32(comp).contiguous()
+        W = w.transpose(1, 2)                                  # [B, out, in]
+    elif nk is not None:
+        if w.dim() != 4 or w.shape[0] != R:
+            raise UnsupportedArch(f"{name}: block weight shape")
+        W = torch.stack([torch.block_diag(*w[r]) for r in range(R)]).transpose(1, 2)
+    else:
+        if w.dim() != 3 or w.shape[0] != R:
+            raise UnsupportedArch(f"{name}: weight shape does not match num_relations")
+        W = w.transpose(1, 2)                                  # [R, out, in]
+    W = W.to(torch.float32).contiguous()
+    root = getattr(conv, "root", None)
+    root = _f32(root).t().contiguous() if root is not None else None
+    if root is not None and tuple(root.shape) != tuple(W.shape[1:]):
+        raise UnsupportedArch(f"{name}: root shape does not match the relation weights (bipartite input)")
+    b = _f32(conv.bias) if getattr(conv, "bias", None) is not None else None
+    term = Term("rel", -1, W, num_relations=R, norm=_REL_NORM[aggr], slices=int(W.shape[0]), coef=coef)
+    return [term], b, root, int(W.shape[2]), int(W.shape[1])
+
+
+def relation_weights(term):
+    """The dense effective weights [num_relations, f_out, f_in] of a "rel" term: its own, or the
+    bases folded with their coefficients in fp64 and rounded once (layer-1 tables)."""
+    if term.coef is None:
+        return term.weight
+    return torch.einsum("rb,boi->roi", term.coef.double(), term.weight.double()).to(torch.float32)
+
+
+def check_rel_features(prog, feat):
+    """Featureless RGCN (node indices in place of a feature matrix) has no lowering."""
+    if any(t.kind == "rel" for c in prog.convs for t in c.terms) and \
+            (feat is None or not torch.is_floating_point(feat)):
+        raise UnsupportedArch("featureless RGCNConv (x as node indices)")
+
+
 def _single_conv_terms(conv, rel, attention=False, bipartite=False):
     name = type(conv).__name__
+    if _is_rgcn(conv):
+        raise UnsupportedArch(f"{name} inside HeteroConv")
     if attention and _is_gat(conv):
         return _gat_terms(conv, rel, bipartite)
     if name == "GCNConv":
@@ -322,6 +398,9 @@ def _conv_layer(conv, rel_index, attention=False):
             f_in, f_out = fi, fo
         if not terms:
             raise UnsupportedArch("HeteroConv with no relation present in the graph")
+    elif _is_rgcn(conv):
+        # typed edges: the relations are the conv's own (edge_type), whatever the graph names
+        terms, bias, root, f_in, f_out = _rgcn_terms(conv)
     else:
         if rel_index is not None and len(rel_index) != 1:
             raise UnsupportedArch("homogeneous conv on a multi-relation graph")
@@ -451,6 +530,9 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
         i += 1
     if not prog.convs:
         raise UnsupportedArch("arch has no GCNConv/SAGEConv/HeteroConv layer first")
+    typed = [any(t.kind == "rel" for t in c.terms) for c in prog.convs]
+    if any(typed) and not all(typed):
+        raise UnsupportedArch("a model mixing RGCNConv with another conv kind")
     while i < len(units) and _is_linear(units[i]):
         lin = units[i]
         act = None
@@ -481,6 +563,6 @@ def count_message_passing(arch: nn.Module) -> int:
     for m in arch.modules():
         if any(c.__name__ == "MessagePassing" for c in type(m).__mro__):
             n += 1
-        elif type(m).__name__ in ("GCNConv", "SAGEConv", "GATConv", "GINConv", "GraphConv"):
+        elif type(m).__name__ in ("GCNConv", "SAGEConv", "GATConv", "GINConv", "GraphConv") + _RGCN_NAMES:
             n += 1
     return n

@@ -31,7 +31,9 @@
  *                                        (wlm.py:349-436 -> data.py:591-648, model.py:62-116,
  *                                        model.py:295-328) for GCNConv / SAGEConv (mean, add, max) /
  *                                        GraphConv / GINConv / GATConv / HeteroConv-sum conv
- *                                        stacks with a dense head; with edge_masks set, the
+ *                                        stacks and RGCNConv / FastRGCNConv stacks on typed
+ *                                        edges (the 4-argument call of model.py:102-112) with a
+ *                                        dense head; with edge_masks set, the
  *                                        edge problem's Data.perturb_edge (data.py:500-554: mask
  *                                        columns are edges) and a dot-product link decoder
  *   xpg_forward_describe / xpg_wide_variants — none: host queries of xpg_masked_forward's own
@@ -55,7 +57,7 @@
 extern "C" {
 #endif
 
-#define XPG_ABI_VERSION 25
+#define XPG_ABI_VERSION 26
 #define XPG_MAX_TERMS 8
 
 typedef void* xpg_stream_t; /* hipStream_t */
@@ -71,7 +73,8 @@ enum xpg_term { XPG_TERM_GCN = 0,   /* D^-1/2 (A_r + I) D^-1/2 over relation r  
                 XPG_TERM_ROOT = 2,  /* the target's own row (SAGE lin_r)                     */
                 XPG_TERM_ATT = 3,   /* graph attention over relation r (GATConv, v22; below)  */
                 XPG_TERM_SUM = 4,   /* sum over kept in-edges of relation r (v25; below)      */
-                XPG_TERM_MAX = 5    /* element-wise max over kept in-edges (v25; below)       */ };
+                XPG_TERM_MAX = 5,   /* element-wise max over kept in-edges (v25; below)       */
+                XPG_TERM_REL = 6    /* every relation's mean / sum, one term (RGCN, v26; below) */ };
 /* SUM and MAX (v25; node masks only: a plan with edge_masks set and one of them is refused).  The
  * edge set of target t in mask row b for relation r is MEAN's: every CSR in-edge (u -> t) with
  * bit(b, u) & bit(b, t), duplicate edges as separate entries, plus self_mult[r][t] copies of
@@ -85,6 +88,27 @@ enum xpg_term { XPG_TERM_GCN = 0,   /* D^-1/2 (A_r + I) D^-1/2 over relation r  
  * at layer 1 it needs the raw form (xpg_layer_desc.weight below).  SUM runs on the multi-kernel
  * and rows paths, MAX and raw layers on the multi-kernel path only; the fused and wide paths
  * take neither kind. */
+/* REL (v26; RGCNConv / FastRGCNConv of PyG 2.0.4; node masks only, no tgt_type): ONE term for all
+ * n_rel relations (edge types) of the plan; its `rel` is ignored.  The edge set of target t in
+ * mask row b for relation r is MEAN's (above): CSR in-edges (u -> t) with bit(b, u) & bit(b, t),
+ * duplicates as separate entries, plus self_mult[r][t] copies of the own row iff bit(b, t): a
+ * (t -> t) edge is an ordinary edge of its relation.  A_r = the sum of the source rows over that
+ * set, divided by its size (norm = XPG_REL_MEAN; an empty set gives 0) or as it is (XPG_REL_SUM).
+ * A masked-out target aggregates 0 and keeps its ROOT term (features are never masked).
+ * A layer with a REL term holds exactly one, first, and at most one ROOT term after it; a plan
+ * with a REL layer has one in every conv layer.  The kernel reads the mask bits itself (f0_node), so such a
+ * plan launches no degree pass and its workspace has no degree region.  Per layer the plan
+ * lists, for every target, the relations that have an in-edge or a self-loop, ascending
+ * (xpg_layer_desc.seg_ptr / seg_rel): only those are visited.
+ * Layer 1 (table form): `table` = [n_rel][n0][f_out_pad], relation r's pre-transformed F_0 rows
+ * X[F_0] W_r (bases folded into W_r by the caller); n_slices = n_rel, coef = NULL; the term adds
+ * sum_r A_r over the rows of table r.
+ * Layer >= 2 (aggregate-then-transform): the term fills n_slices <= 32 slices of the layer's
+ * dense input, slice s = A_s (coef = NULL, and then n_slices = n_rel) or sum_r coef[r][s] A_r
+ * (coef = device [n_rel][n_slices], the basis coefficients: any n_rel); the ROOT term's slice
+ * follows, and `weight` is [f_out_pad][(n_slices + ROOT terms) * f_in_pad].
+ * REL plans run on the multi-kernel path only: the rows, fused and wide paths decline them. */
+enum xpg_rel_norm { XPG_REL_MEAN = 0, XPG_REL_SUM = 1 };
 
 int xpg_abi_version(void);
 const char* xpg_last_error(void);
@@ -257,6 +281,10 @@ typedef struct xpg_term_desc {
   int32_t self_loops;      /* GATConv add_self_loops                                      */
   const float* att_src;
   const float* att_dst;
+  /* XPG_TERM_REL only (v26; the rules are above) */
+  int32_t n_slices;        /* slices of the dense input (layer >= 2); layer 1: n_rel        */
+  int32_t norm;            /* enum xpg_rel_norm                                            */
+  const float* coef;       /* device [n_rel][n_slices]; NULL = identity (n_slices == n_rel) */
 } xpg_term_desc;
 
 typedef struct xpg_layer_desc {
@@ -278,7 +306,8 @@ typedef struct xpg_layer_desc {
   const int32_t* self_mult;/* [n_rel * n_tgt] multiplicity of (t, t) edges             */
   xpg_term_desc terms[XPG_MAX_TERMS];
   const float* weight;     /* layer >= 2: [f_out_pad][n_terms * f_in_pad] (ATT layers:   */
-                           /* [f_out_pad][(sum of the terms' heads) * f_in_pad])         */
+                           /* [f_out_pad][(sum of the terms' heads) * f_in_pad]; REL     */
+                           /* layers: [f_out_pad][(n_slices + ROOT terms) * f_in_pad])   */
   /* Raw layer 1 (v25): layers[0].weight != NULL and layers[0].f_in_pad > 0 (the first conv's
    * input width rounded up to 32, at most 256) make layer 1 aggregate-then-transform like the
    * deeper layers: every term's `table` is the one pointer to the zero-padded raw feature rows
@@ -294,6 +323,9 @@ typedef struct xpg_layer_desc {
   const int32_t* agg_eid;  /* [n_edges] mask column (subgraph edge id) of each in-edge   */
   const int32_t* self_ptr; /* [n_rel * (n_tgt + 1)] self-loop edges of each target       */
   const int32_t* self_eid; /* their mask columns (MEAN terms count the kept ones)        */
+  /* layers with a REL term only (v26; NULL otherwise):                                     */
+  const int32_t* seg_ptr;  /* [n_tgt + 1] each target's range of seg_rel                 */
+  const int32_t* seg_rel;  /* relations with an in-edge or self-loop at the target, ascending */
 } xpg_layer_desc;
 
 typedef struct xpg_head_desc {
