@@ -11,7 +11,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libxpgnn.so")
-ABI_VERSION = 26
+ABI_VERSION = 27
 MAX_TERMS = 8
 
 ACT = {None: 0, "identity": 0, "relu": 1, "sigmoid": 2, "tanh": 3, "leaky_relu": 4, "elu": 5}
@@ -59,7 +59,7 @@ class ForwardPlanDesc(ctypes.Structure):
                 ("layers", ctypes.POINTER(LayerDesc)), ("n_head", c_i32),
                 ("head", ctypes.POINTER(HeadDesc)), ("out_col", c_i32),
                 ("edge_masks", c_i32), ("deg_eid", c_vp), ("edge_dot", c_i32), ("dot_a", c_i32),
-                ("dot_b", c_i32), ("dot_act", c_i32)]
+                ("dot_b", c_i32), ("dot_act", c_i32), ("dot_scale", c_vp)]
 
 
 class WlmParams(ctypes.Structure):

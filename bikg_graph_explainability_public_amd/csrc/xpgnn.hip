@@ -1325,17 +1325,31 @@ struct RelArgs {
   const float* bias;  // layer 1 epilogue
   int act;
   int f_real;
+  // edge masks (EM kernels only): in-edge e kept iff bit agg_eid[e] of the row; the self term =
+  // the number of kept self-loop edges of the relation (self_ptr / self_eid)
+  const int32_t* agg_eid;
+  const int32_t* self_ptr;
+  const int32_t* self_eid;
 };
 
 // Relation r's aggregate at target t for the lane's float4 chunk: the MEAN branch of k_agg
 // (EB in-edges per round: their keep tests, then the kept rows, issued together before the first
 // add; the adds in edge order), with a source's keep test read from the mask row itself.  The
-// caller has found the target kept.
-template <bool L1>
+// caller has found the target kept.  EM (edge masks): an in-edge's keep test is its own column's
+// bit (agg_eid, no f0_node step) and the self multiplicity is the count of the relation's kept
+// self-loop columns at the target.
+template <bool L1, bool EM>
 __device__ __forceinline__ float4 rel_segment(const RelArgs& a, const uint32_t* mrow, const float* base, int r,
                                               int t, int self_pos, int sub) {
   const int* pp = a.agg_ptr + (int64_t)r * (a.n_tgt + 1);
-  const int sm = a.self_mult[(int64_t)r * a.n_tgt + t];
+  int sm;
+  if (EM) {
+    const int* sp = a.self_ptr + (int64_t)r * (a.n_tgt + 1);
+    sm = 0;
+    for (int e = sp[t]; e < sp[t + 1]; ++e) sm += bit_of(mrow, a.self_eid[e]);
+  } else {
+    sm = a.self_mult[(int64_t)r * a.n_tgt + t];
+  }
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
   if (sm > 0) fma4(s, static_cast<float>(sm), reinterpret_cast<const float4*>(base + (int64_t)self_pos * a.width)[sub]);
   int cnt = sm;
@@ -1347,11 +1361,18 @@ __device__ __forceinline__ float4 rel_segment(const RelArgs& a, const uint32_t* 
 #pragma unroll
     for (int q = 0; q < EB; ++q) {
       const int e = eb + q < e_end ? eb + q : eb;
-      kx[q] = a.agg_f0[e];
-      up[q] = L1 ? kx[q] : a.agg_src[e];
+      if (EM) {
+        kx[q] = a.agg_eid[e];
+        up[q] = L1 ? a.agg_f0[e] : a.agg_src[e];
+      } else {
+        kx[q] = a.agg_f0[e];
+        up[q] = L1 ? kx[q] : a.agg_src[e];
+      }
     }
+    if (!EM) {
 #pragma unroll
-    for (int q = 0; q < EB; ++q) kx[q] = a.f0_node[kx[q]];
+      for (int q = 0; q < EB; ++q) kx[q] = a.f0_node[kx[q]];
+    }
 #pragma unroll
     for (int q = 0; q < EB; ++q) kp[q] = bit_of(mrow, kx[q]) && eb + q < e_end;
     float4 v[EB];
@@ -1379,8 +1400,9 @@ __device__ __forceinline__ float4 rel_segment(const RelArgs& a, const uint32_t* 
 // = relation r's aggregate (zeros for relations the target does not see: the segment list is
 // ascending, one pass); with COEF slice s = sum_r coef[r][s] A_r, G slices at a time in
 // compile-time-indexed accumulators, the segments walked again per group of G; then the ROOT
-// slices, the target's own row.
-template <bool L1, bool COEF>
+// slices, the target's own row.  EM: an edge-mask plan, where no node is masked (every target is
+// on) and rel_segment tests edge columns.
+template <bool L1, bool COEF, bool EM>
 __global__ __launch_bounds__(256) void k_agg_rel(RelArgs a) {
   const int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   const int64_t item = gid / a.lps;
@@ -1391,14 +1413,14 @@ __global__ __launch_bounds__(256) void k_agg_rel(RelArgs a) {
   const uint32_t* mrow = a.bits + b * a.words;
   const int t0 = a.tgt_f0[t];
   const int tp = a.tgt_prev[t];
-  const bool t_on = bit_of(mrow, a.f0_node[t0]);
+  const bool t_on = EM ? true : bit_of(mrow, a.f0_node[t0]);
   const int sg0 = a.seg_ptr[t];
   const int sg1 = t_on ? a.seg_ptr[t + 1] : sg0;
   if (L1) {
     float4 tot = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int sg = sg0; sg < sg1; ++sg) {
       const int r = a.seg_rel[sg];
-      const float4 s = rel_segment<true>(a, mrow, a.table + (int64_t)r * a.n0 * a.width, r, t, t0, sub);
+      const float4 s = rel_segment<true, EM>(a, mrow, a.table + (int64_t)r * a.n0 * a.width, r, t, t0, sub);
       tot.x += s.x; tot.y += s.y; tot.z += s.z; tot.w += s.w;
     }
     if (a.root) {
@@ -1420,7 +1442,7 @@ __global__ __launch_bounds__(256) void k_agg_rel(RelArgs a) {
     for (int r = 0; r < a.n_slices; ++r) {
       float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
       if (sg < sg1 && a.seg_rel[sg] == r) {
-        s = rel_segment<false>(a, mrow, base, r, t, tp, sub);
+        s = rel_segment<false, EM>(a, mrow, base, r, t, tp, sub);
         ++sg;
       }
       o[(int64_t)r * w4] = s;
@@ -1433,7 +1455,7 @@ __global__ __launch_bounds__(256) void k_agg_rel(RelArgs a) {
       for (int j = 0; j < G; ++j) acc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
       for (int sg = sg0; sg < sg1; ++sg) {
         const int r = a.seg_rel[sg];
-        const float4 s = rel_segment<false>(a, mrow, base, r, t, tp, sub);
+        const float4 s = rel_segment<false, EM>(a, mrow, base, r, t, tp, sub);
         const float* cf = a.coef + (int64_t)r * a.n_slices + g0;
 #pragma unroll
         for (int j = 0; j < G; ++j) fma4(acc[j], g0 + j < a.n_slices ? cf[j] : 0.f, s);
@@ -1628,6 +1650,19 @@ __global__ void k_edge_dot(const float* __restrict__ C, int64_t rows, int n_tgt,
   const float* cb = C + (r * n_tgt + tb) * ldc;
   float s = 0.f;
   for (int f = 0; f < n; ++f) s = fmaf(ca[f], cb[f], s);
+  y[r] = act_apply(s, act);
+}
+
+// k_edge_dot with a per-column scale d [n] (the DistMult relation embedding of the plan's query
+// edge type): y[r] = act(sum_f (C[r][a][f] d[f]) C[r][b][f]), fixed fma order.
+__global__ void k_edge_dot_scaled(const float* __restrict__ C, int64_t rows, int n_tgt, int64_t ldc, int n, int ta,
+                                  int tb, int act, const float* __restrict__ d, float* __restrict__ y) {
+  const int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (r >= rows) return;
+  const float* ca = C + (r * n_tgt + ta) * ldc;
+  const float* cb = C + (r * n_tgt + tb) * ldc;
+  float s = 0.f;
+  for (int f = 0; f < n; ++f) s = fmaf(ca[f] * d[f], cb[f], s);
   y[r] = act_apply(s, act);
 }
 
@@ -6001,7 +6036,7 @@ bool plan_has_rel(const xpg_forward_plan* p) {
 // an all-attention plan reads no in-degrees: k_degree is not launched for it; nor for a REL plan
 // (every conv layer holds a REL term, rel_plan_check), whose kernel reads the mask bits itself
 bool plan_needs_degree(const xpg_forward_plan* p) {
-  if (plan_has_rel(p)) return p->edge_masks != 0;
+  if (plan_has_rel(p)) return false;  // edge masks included: the EM kernels test the edge columns
   for (int l = 0; l < p->n_layers; ++l)
     for (int k = 0; k < p->layers[l].n_terms && k < XPG_MAX_TERMS; ++k)
       if (p->layers[l].terms[k].kind != XPG_TERM_ATT) return true;
@@ -6250,8 +6285,11 @@ int launch_att_layer(const xpg_forward_plan* p, int l, const uint32_t* bits, int
 // The argument rules of REL plans (xpgnn.h), checked on the host before anything is launched.
 int rel_plan_check(const xpg_forward_plan* p) {
   if (!plan_has_rel(p)) return XPG_OK;
-  XPG_REQ(!p->edge_masks, "masked_forward: REL terms do not take edge-mask plans");
   XPG_REQ(p->f0_node, "masked_forward: REL terms need f0_node");
+  if (p->edge_masks)  // v27: taken when every conv layer carries its edge columns
+    for (int l = 0; l < p->n_layers; ++l)
+      XPG_REQ(p->layers[l].agg_eid && p->layers[l].self_ptr && p->layers[l].self_eid,
+              "masked_forward: REL terms do not take edge-mask plans without agg_eid / self_ptr / self_eid");
   for (int l = 0; l < p->n_layers; ++l) {
     const xpg_layer_desc& ly = p->layers[l];
     XPG_REQ(ly.n_terms >= 1 && ly.n_terms <= XPG_MAX_TERMS, "layer: 1..8 terms");
@@ -6305,6 +6343,12 @@ int launch_rel_layer(const xpg_forward_plan* p, int l, const uint32_t* bits, int
   a.words = words_of(p->cols);
   a.mean = td.norm == XPG_REL_MEAN;
   a.out = out;
+  const bool em = p->edge_masks != 0;
+  if (em) {
+    a.agg_eid = ly.agg_eid;
+    a.self_ptr = ly.self_ptr;
+    a.self_eid = ly.self_eid;
+  }
   const int64_t threads = rows * ly.n_tgt * a.lps;
   if (threads == 0) return XPG_OK;
   const dim3 grid(static_cast<unsigned>(cdiv(threads, 256))), block(256);
@@ -6315,7 +6359,8 @@ int launch_rel_layer(const xpg_forward_plan* p, int l, const uint32_t* bits, int
     a.bias = ly.bias;
     a.act = ly.act;
     a.f_real = ly.f_out;
-    hipLaunchKernelGGL((k_agg_rel<true, false>), grid, block, 0, st, a);
+    if (em) hipLaunchKernelGGL((k_agg_rel<true, false, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_agg_rel<true, false, false>), grid, block, 0, st, a);
     XPG_LAUNCHED();
     return XPG_OK;
   }
@@ -6324,8 +6369,14 @@ int launch_rel_layer(const xpg_forward_plan* p, int l, const uint32_t* bits, int
   a.n_slices = td.n_slices;
   a.n_root = ly.n_terms - 1;
   a.out_ld = (int64_t)layer_slices(ly) * ly.f_in_pad;
-  if (td.coef) hipLaunchKernelGGL((k_agg_rel<false, true>), grid, block, 0, st, a);
-  else hipLaunchKernelGGL((k_agg_rel<false, false>), grid, block, 0, st, a);
+  if (em) {
+    if (td.coef) hipLaunchKernelGGL((k_agg_rel<false, true, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_agg_rel<false, false, true>), grid, block, 0, st, a);
+  } else if (td.coef) {
+    hipLaunchKernelGGL((k_agg_rel<false, true, false>), grid, block, 0, st, a);
+  } else {
+    hipLaunchKernelGGL((k_agg_rel<false, false, false>), grid, block, 0, st, a);
+  }
   XPG_LAUNCHED();
   return XPG_OK;
 }
@@ -7777,8 +7828,12 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
     const int n_real = p->n_head > 0 ? p->head[p->n_head - 1].n_real : last.f_out;
     XPG_REQ(p->dot_a >= 0 && p->dot_a < last.n_tgt && p->dot_b >= 0 && p->dot_b < last.n_tgt,
             "masked_forward: link decoder targets out of range");
-    hipLaunchKernelGGL(k_edge_dot, dim3(static_cast<unsigned>(cdiv(rows, 256))), dim3(256), 0, st, cur, rows,
-                       last.n_tgt, cur_ld, n_real, p->dot_a, p->dot_b, p->dot_act, y);
+    if (p->dot_scale)
+      hipLaunchKernelGGL(k_edge_dot_scaled, dim3(static_cast<unsigned>(cdiv(rows, 256))), dim3(256), 0, st, cur, rows,
+                         last.n_tgt, cur_ld, n_real, p->dot_a, p->dot_b, p->dot_act, p->dot_scale, y);
+    else
+      hipLaunchKernelGGL(k_edge_dot, dim3(static_cast<unsigned>(cdiv(rows, 256))), dim3(256), 0, st, cur, rows,
+                         last.n_tgt, cur_ld, n_real, p->dot_a, p->dot_b, p->dot_act, y);
   } else {
     hipLaunchKernelGGL(k_take_col, dim3(static_cast<unsigned>(cdiv(M, 256))), dim3(256), 0, st, cur, M, cur_ld,
                        p->out_col, y);

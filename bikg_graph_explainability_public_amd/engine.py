@@ -717,7 +717,10 @@ class ForwardPlan:
         Edge problems (Data.perturb_edge, data.py:500-554): `edge_cols` = per relation the mask
         column of every edge (mask columns are the subgraph's edges; `cols` becomes their
         count) and `link` = (a, b, act): the output is the link decoder act(<h_a, h_b>) of
-        queries a and b instead of one column per query."""
+        queries a and b instead of one column per query; `link` = (a, b, act, d) with a vector d
+        of the output width scales the columns, act(sum_f h_a[f] d[f] h_b[f]) (DistMult, d = the
+        query relation's embedding).  A typed-relation ("rel") program takes one entry of
+        `rel_edges` / `edge_cols` per edge type."""
         device = torch.device(device) if device is not None else sub_feat.device
         _lib.require_device(torch.empty(0, device=device), "plan device")
         if len(program.convs) == 0:
@@ -794,8 +797,6 @@ class ForwardPlan:
                 if len(rel) != 1 or terms[0] is not rel[0] or len(terms) > 2 or \
                         any(t.kind != "root" for t in terms[1:]):
                     raise ValueError("a typed-relation layer holds one rel term and at most one root term")
-                if self.edge_masks:
-                    raise ValueError("rel terms on edge-mask plans are not supported")
                 if program.n_types > 1:
                     raise ValueError("rel terms on multi-node-type programs are not supported")
                 if rel[0].num_relations != self.n_rel:
@@ -996,11 +997,22 @@ class ForwardPlan:
             self._i32(self.desc, "deg_eid", arr["deg_eid"] if arr["deg_eid"].size else np.zeros(1))
         self.link = link
         if link is not None:
-            a, b, act = link
+            a, b, act = link[:3]
             if not (0 <= a < self.n_out and 0 <= b < self.n_out):
                 raise ValueError("link decoder targets out of range")
             self.desc.edge_dot, self.desc.dot_a, self.desc.dot_b = 1, int(a), int(b)
             self.desc.dot_act = ACT[act]
+            if len(link) > 3 and link[3] is not None:
+                # DistMult: the query relation's embedding, zero-padded to the last layer's width
+                n_real = program.head[-1].weight.shape[0] if program.head else program.convs[-1].f_out
+                d = torch.as_tensor(link[3]).detach().reshape(-1)
+                if d.numel() != n_real:
+                    raise ValueError(f"link scale vector of {d.numel()} entries on an output of "
+                                     f"width {n_real}")
+                dp = torch.zeros(prev_pad, dtype=torch.float32, device=device)
+                dp[:n_real] = d.to(device=device, dtype=torch.float32)
+                self._keep.append(dp)
+                self.desc.dot_scale = dp.data_ptr()
             self.n_out = 1
         self._upload_i32()
         self._ws = None

@@ -101,8 +101,9 @@ class Explainer:
     def edge_masks(self):
         """Non-compat edge problems (params["edge_masks"] = True): mask columns
         are the computational graph's edges (Data.perturb_edge, data.py:500-554) and the arch is
-        an edge-level model (nn.LinkModel).  Off (default), edge problems fail as the reference's
-        do (masks.py:294)."""
+        an edge-level model (nn.LinkModel; with `edge_types` on a graph without type names, the
+        typed nn.RelLinkModel).  Off (default), edge problems fail as the reference's do
+        (masks.py:294)."""
         return "edge" in self.problem and bool(self.params.get("edge_masks", False))
 
     @staticmethod
@@ -306,16 +307,26 @@ class Explainer:
         data = Data(feat, ei)
         sub_pw = sub_pw_names = None
         sub_nt = sub_et = None
-        link = pos = None
+        link = pos = label_type = None
         if self.edge_masks:
             # edge problem, edge masks (non-compat: the reference's edge path is broken at
             # masks.py:294 and data.py:331): mask columns = the computational graph's edges
-            if h_etypes is not None or node_types is not None or edge_types is not None:
+            # typed edges (edge_types on a graph without type names: a relational link model,
+            # nn.RelLinkModel) are taken with one node type; named types (HeteroData) are not
+            if h_etypes is not None or h_ntypes is not None:
                 raise NotImplementedError("edge masks: homogeneous graphs only")
+            if node_types is not None and torch.unique(node_types).numel() > 1:
+                raise NotImplementedError("edge masks: one node type only")
             n_hops = Model(self.arch).get_hops(0)
             ind = self.extract_index(element, names)
             sub_feat, sub_ei, sub_names, sub_ind, link, pos = data.edge_comp_graph(
                 ind, n_hops, names, return_pos=True)
+            if edge_types is not None:
+                et = edge_types.reshape(-1)
+                if et.numel() != ei.shape[1]:
+                    raise ValueError("edge_types must give one type per edge")
+                sub_et = et[torch.as_tensor(pos, device=et.device)]
+                label_type = int(et[ind])  # the label type: the query edge's own
             if pathways is not None:
                 sub_pw, sub_pw_names, _ = Pathways(pathways, pathway_names,
                                                    pathway_types).comp_graph(sub_names)
@@ -351,9 +362,9 @@ class Explainer:
         if isinstance(sub_ind, torch.Tensor):
             sub_ind = int(sub_ind.reshape(-1)[0])
         S = Data(sub_feat, sub_ei).element_size(self.problem)
-        return {"link": link, "sub_feat": sub_feat, "sub_ei": sub_ei, "sub_names": sub_names,
-                "sub_ind": sub_ind, "sub_nt": sub_nt, "sub_et": sub_et, "h_ntypes": h_ntypes,
-                "h_etypes": h_etypes, "padded_dims": padded_dims, "sub_pw": sub_pw,
+        return {"link": link, "label_type": label_type, "sub_feat": sub_feat, "sub_ei": sub_ei,
+                "sub_names": sub_names, "sub_ind": sub_ind, "sub_nt": sub_nt, "sub_et": sub_et,
+                "h_ntypes": h_ntypes, "h_etypes": h_etypes, "padded_dims": padded_dims, "sub_pw": sub_pw,
                 "sub_pw_names": sub_pw_names, "sub_pw_inds": sub_pw_inds, "S": S,
                 "has_pathways": pathways is not None, "ind": ind,
                 "pos": tuple(pos.tolist()) if pos is not None else None,
@@ -461,13 +472,16 @@ class Explainer:
         w0_dev = engine.h2d(w0_all.numpy(), device)
 
         clock.mark("plan")
+        # typed edge problems (nn.RelLinkModel): the subgraph's edge types and the query's own
+        typed = {"edge_type": c["sub_et"], "label_type": c["label_type"]} if self.edge_masks else {}
 
         if cached:
             plan, verify = cached[1], None
         elif self.edge_masks:
             plan = pipeline.build_edge_plan(self.arch, sub_feat, sub_ei, *c["link"],
-                                            module_state=mstate)
-            verify = lambda: pipeline.verify_edge_plan(plan, self.arch, sub_feat, sub_ei, *c["link"])
+                                            module_state=mstate, **typed)
+            verify = lambda: pipeline.verify_edge_plan(plan, self.arch, sub_feat, sub_ei, *c["link"],
+                                                       **typed)
         else:
             plan = pipeline.build_plan(self.arch, sub_feat, sub_ei, [sub_ind], *geo,
                                        module_state=mstate, attention=self.attention_engine)
@@ -483,7 +497,7 @@ class Explainer:
             if verify is None:
                 verify = lambda: pipeline.verify_plan(plan, self.arch, sub_feat, sub_ei, sub_ind, *geo) \
                     if not self.edge_masks else pipeline.verify_edge_plan(plan, self.arch, sub_feat, sub_ei,
-                                                                          *c["link"])
+                                                                          *c["link"], **typed)
             # the check guards the arch lowering (program.compile_arch + the plan's term
             # dropping), which depends on the module, the graph's type structure and the query
             # layer's node types: once per module state (parameter storage + in-place version
@@ -537,7 +551,7 @@ class Explainer:
                 ys = [pipeline.generic_edge_outputs(
                     self.arch, sub_feat, sub_ei,
                     engine.unpack_masks(bits[i], S) if masks[i] is None else masks[i],
-                    *c["link"], max_rows=batch) for i in range(t0, t1)]
+                    *c["link"], max_rows=batch, **typed) for i in range(t0, t1)]
                 return torch.stack(ys) if ys else torch.empty((0, R), device=device)
             y = sharding.gather_map(times, generic, g)
         else:

@@ -573,3 +573,49 @@ class LinkModel(nn.Module):
         eli = edge_index if edge_label_index is None else edge_label_index
         s = (z[eli[0]] * z[eli[1]]).sum(-1, keepdim=True)
         return torch.sigmoid(s) if self.act == "sigmoid" else s
+
+
+class RelLinkModel(nn.Module):
+    """Edge-level model of a typed-edge graph (the knowledge-graph link predictor): a relational
+    encoder called `encoder(x, edge_index, node_types, edge_types)` (e.g. RGCNStack with
+    final_act="identity"; fc_dims of one width = no head) and a DistMult decoder,
+    score(u, r, v) = act(sum_f z_u[f] rel_emb[r][f] z_v[f]), or decoder="dot" (no `rel_emb`, the
+    factor is 1).
+
+    forward(x, edge_index, node_types, edge_types, edge_label_index=None, edge_label_type=None)
+    scores the edges of `edge_label_index` with types `edge_label_type` (defaults: every edge of
+    `edge_index` with its own type) -> [n_label, 1].  As with LinkModel, a separate label index
+    keeps the query edge's score defined when its own column is masked out."""
+
+    def __init__(self, encoder, num_relations, decoder="distmult", act="sigmoid"):
+        super().__init__()
+        if act not in ("sigmoid", "identity", None):
+            raise ValueError("RelLinkModel act must be 'sigmoid' or 'identity'")
+        if decoder not in ("distmult", "dot"):
+            raise ValueError("RelLinkModel decoder must be 'distmult' or 'dot'")
+        self.encoder = encoder
+        self.num_relations = int(num_relations)
+        self.decoder = decoder
+        self.act = act or "identity"
+        if decoder == "distmult":
+            width = None
+            for m in encoder.modules():  # the encoder's output width: its last Linear / RGCNConv
+                if hasattr(m, "out_channels"):
+                    width = int(m.out_channels)
+            if width is None:
+                raise ValueError("RelLinkModel cannot tell the encoder's output width")
+            self.rel_emb = nn.Parameter(torch.empty(self.num_relations, width))
+            _uniform_(self.rel_emb, math.sqrt(6.0 / (self.num_relations + width)))  # glorot
+        else:
+            self.register_parameter("rel_emb", None)
+
+    def forward(self, x, edge_index, node_types, edge_types, edge_label_index=None,
+                edge_label_type=None):
+        z = self.encoder(x, edge_index, node_types, edge_types)
+        eli = edge_index if edge_label_index is None else edge_label_index
+        s = z[eli[0].long()]
+        if self.rel_emb is not None:
+            elt = edge_types if edge_label_type is None else edge_label_type
+            s = s * self.rel_emb[elt.reshape(-1).long()]
+        s = (s * z[eli[1].long()]).sum(-1, keepdim=True)
+        return torch.sigmoid(s) if self.act == "sigmoid" else s

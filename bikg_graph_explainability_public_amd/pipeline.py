@@ -41,8 +41,10 @@ def typed_relations(prog):
     return counts.pop() if counts else 0
 
 
-def typed_relation_edges(edge_index, edge_type, n_rel):
-    """relation_edges for a typed-relation program: it needs the edge types, all inside [0, n_rel)."""
+def typed_relation_edges(edge_index, edge_type, n_rel, return_order=False):
+    """relation_edges for a typed-relation program: it needs the edge types, all inside [0, n_rel).
+    return_order: also the sort's permutation (each edge's position in `edge_index`, relation by
+    relation): the mask columns of an edge-mask plan."""
     if edge_type is None:
         raise ValueError("a RGCNConv model needs edge_types")
     et = edge_type.reshape(-1)
@@ -54,7 +56,8 @@ def typed_relation_edges(edge_index, edge_type, n_rel):
     # selections: each relation's edges in edge order, as relation_edges gives them
     ei, et = edge_index.detach().cpu(), et.detach().cpu().long()
     order = torch.argsort(et, stable=True)
-    return list(torch.split(ei[:, order], torch.bincount(et, minlength=n_rel).tolist(), dim=1))
+    rels = list(torch.split(ei[:, order], torch.bincount(et, minlength=n_rel).tolist(), dim=1))
+    return (rels, order) if return_order else rels
 
 
 _PROGRAMS = collections.OrderedDict()  # compiled_program's cache: key -> (weakref(arch), program)
@@ -150,12 +153,18 @@ def build_plan(arch, feat, edge_index, queries, node_type=None, edge_type=None,
     return plan
 
 
-def build_edge_plan(arch, feat, edge_index, u, v, module_state=None):
+def build_edge_plan(arch, feat, edge_index, u, v, module_state=None, edge_type=None,
+                    label_type=None):
     """ForwardPlan of an edge problem (edge masks, Data.perturb_edge data.py:500-554): mask
     columns = the subgraph's edges, output = the LinkModel decoder's score of edge (u, v).
-    None when the engine cannot compile `arch` (generic torch path)."""
+    None when the engine cannot compile `arch` (generic torch path).
+
+    A typed-relation program (nn.RelLinkModel over RGCNConv layers) takes `edge_type` (one type
+    per subgraph edge) as its relations and `label_type`, the query edge's type, which picks the
+    DistMult decoder's relation embedding."""
     try:
         prog = compiled_program(arch, state=module_state)
+        check_rel_features(prog, feat)
     except UnsupportedArch as e:
         warnings.warn(f"engine cannot compile arch ({e}); using the generic torch path")
         return None
@@ -166,20 +175,40 @@ def build_edge_plan(arch, feat, edge_index, u, v, module_state=None):
     queries, link = ([u, v], (0, 1, prog.link_act)) if u != v else ([u], (0, 0, prog.link_act))
     cols = torch.arange(edge_index.shape[1], device=edge_index.device)
     try:
+        typed = typed_relations(prog)
+        if typed:
+            # each relation's edges in edge order, with their positions in the subgraph's edge
+            # list (the mask columns) in that same order
+            rels, order = typed_relation_edges(edge_index, edge_type, typed, return_order=True)
+            ecols = list(torch.split(order, [e.shape[1] for e in rels]))
+            d = None
+            if prog.link_rel is not None:
+                if label_type is None or not 0 <= int(label_type) < prog.link_rel.shape[0]:
+                    raise ValueError("the query edge's type is missing or has no relation embedding")
+                d = prog.link_rel[int(label_type)]
+            return engine.ForwardPlan(prog, feat, rels, queries, edge_cols=ecols, link=link + (d,))
         return engine.ForwardPlan(prog, feat, [edge_index], queries, edge_cols=[cols], link=link)
     except ValueError as e:
         warnings.warn(f"engine plan rejected ({e}); using the generic torch path")
         return None
 
 
-def generic_edge_outputs(arch, feat, edge_index, mask, u, v, max_rows=None):
+def generic_edge_outputs(arch, feat, edge_index, mask, u, v, max_rows=None, edge_type=None,
+                         label_type=None):
     """Edge problem through the user's module (torch, on the device): the B-fold union graph of
     Data.perturbator with perturb_edge (data.py:591-648, 500-554: copy b keeps edge e iff
     mask[b, e], copy-major order, node ids shifted by b * N) and `arch(x, ei,
-    edge_label_index=...)` scoring each copy's (u, v) -> y [B]."""
+    edge_label_index=...)` scoring each copy's (u, v) -> y [B].
+
+    With `edge_type` (one type per edge) and `label_type` (the query edge's type) the module is a
+    typed link model (nn.RelLinkModel) and is called `arch(x, ei, None, et, edge_label_index=...,
+    edge_label_type=...)`: the kept edges' types follow the kept edges."""
     B, _ = mask.shape
     N = feat.shape[0]
     step = B if max_rows is None else max_rows
+    typed = edge_type is not None and label_type is not None
+    if typed:
+        edge_type = edge_type.reshape(-1).to(edge_index.device)
     ys = []
     for b0 in range(0, B, step):
         m = mask[b0:b0 + step]
@@ -190,16 +219,23 @@ def generic_edge_outputs(arch, feat, edge_index, mask, u, v, max_rows=None):
         off = torch.arange(nb, device=feat.device) * N
         eli = torch.stack([off + u, off + v])
         with torch.no_grad():
-            ys.append(arch(x, ei, edge_label_index=eli).reshape(-1).float())
+            if typed:
+                lt = torch.full((nb,), int(label_type), dtype=torch.long, device=feat.device)
+                out = arch(x, ei, None, edge_type[cols], edge_label_index=eli, edge_label_type=lt)
+            else:
+                out = arch(x, ei, edge_label_index=eli)
+            ys.append(out.reshape(-1).float())
     return torch.cat(ys)
 
 
-def verify_edge_plan(plan, arch, feat, edge_index, u, v, rows=8, tol=1e-4):
+def verify_edge_plan(plan, arch, feat, edge_index, u, v, rows=8, tol=1e-4, edge_type=None,
+                     label_type=None):
     """The compiled edge plan against the user's module on a few random edge masks."""
     g = torch.Generator(device="cpu").manual_seed(1234)
     mask = (torch.rand((rows, edge_index.shape[1]), generator=g) < 0.5).to(feat.device)
     mask[0] = True
-    ref = generic_edge_outputs(arch, feat, edge_index, mask, u, v)
+    ref = generic_edge_outputs(arch, feat, edge_index, mask, u, v, edge_type=edge_type,
+                               label_type=label_type)
     got = plan.forward(engine.pack_masks(mask))[:, 0]
     err = (ref - got).abs().max().item()
     return err <= tol * max(1.0, ref.abs().max().item()), err

@@ -81,6 +81,9 @@ class ModelProgram:
     n_types: int = 1               # > 1: multi-node-type program (node-type-gated terms)
     out_type: Optional[int] = None  # multi-node-type: node type whose rows feed the head
     link_act: Optional[str] = None  # LinkModel: the program is its encoder; decoder act(<z_u, z_v>)
+    # RelLinkModel's DistMult decoder: fp32 [num_relations, C] relation embeddings, the score of a
+    # type-r edge is act(sum_f z_u[f] link_rel[r][f] z_v[f]); None: the plain dot product
+    link_rel: Optional[torch.Tensor] = None
     # ROOT-only conv layers that are the second Linear of a GINConv MLP: no message passing of
     # their own (the module's hop count, count_message_passing, does not include them)
     extra_layers: int = 0
@@ -490,6 +493,19 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
     if type(arch).__name__ == "LinkModel" and hasattr(arch, "encoder"):
         prog = compile_arch(arch.encoder, edge_type_names, node_type_names, attention)
         prog.link_act = getattr(arch, "act", "identity") or "identity"
+        return prog
+    if type(arch).__name__ == "RelLinkModel" and hasattr(arch, "encoder"):
+        prog = compile_arch(arch.encoder, edge_type_names, node_type_names, attention)
+        if not all(any(t.kind == "rel" for t in c.terms) for c in prog.convs):
+            raise UnsupportedArch("RelLinkModel needs an encoder of RGCNConv layers")
+        prog.link_act = getattr(arch, "act", "identity") or "identity"
+        emb = getattr(arch, "rel_emb", None)
+        if emb is not None:
+            width = prog.head[-1].weight.shape[0] if prog.head else prog.convs[-1].f_out
+            if emb.dim() != 2 or emb.shape[1] != width:
+                raise UnsupportedArch(f"rel_emb of width {tuple(emb.shape)[-1]} on an encoder "
+                                      f"output of width {width}")
+            prog.link_rel = _f32(emb)
         return prog
     rel_index = None
     if edge_type_names is not None:

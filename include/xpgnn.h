@@ -35,7 +35,8 @@
  *                                        edges (the 4-argument call of model.py:102-112) with a
  *                                        dense head; with edge_masks set, the
  *                                        edge problem's Data.perturb_edge (data.py:500-554: mask
- *                                        columns are edges) and a dot-product link decoder
+ *                                        columns are edges) and a dot-product or DistMult link
+ *                                        decoder (GCN / SAGE-mean terms, or RGCN REL terms, v27)
  *   xpg_forward_describe / xpg_wide_variants — none: host queries of xpg_masked_forward's own
  *                                        dispatch (path and wide-path kernels), for tests and logs
  *   xpg_sampler_describe               — none: host query of the device samplers' own dispatch (which
@@ -57,7 +58,7 @@
 extern "C" {
 #endif
 
-#define XPG_ABI_VERSION 26
+#define XPG_ABI_VERSION 27
 #define XPG_MAX_TERMS 8
 
 typedef void* xpg_stream_t; /* hipStream_t */
@@ -88,7 +89,8 @@ enum xpg_term { XPG_TERM_GCN = 0,   /* D^-1/2 (A_r + I) D^-1/2 over relation r  
  * at layer 1 it needs the raw form (xpg_layer_desc.weight below).  SUM runs on the multi-kernel
  * and rows paths, MAX and raw layers on the multi-kernel path only; the fused and wide paths
  * take neither kind. */
-/* REL (v26; RGCNConv / FastRGCNConv of PyG 2.0.4; node masks only, no tgt_type): ONE term for all
+/* REL (v26; RGCNConv / FastRGCNConv of PyG 2.0.4; no tgt_type; the node-mask rules first, the
+ * edge-mask rules of v27 at the end): ONE term for all
  * n_rel relations (edge types) of the plan; its `rel` is ignored.  The edge set of target t in
  * mask row b for relation r is MEAN's (above): CSR in-edges (u -> t) with bit(b, u) & bit(b, t),
  * duplicates as separate entries, plus self_mult[r][t] copies of the own row iff bit(b, t): a
@@ -107,7 +109,17 @@ enum xpg_term { XPG_TERM_GCN = 0,   /* D^-1/2 (A_r + I) D^-1/2 over relation r  
  * dense input, slice s = A_s (coef = NULL, and then n_slices = n_rel) or sum_r coef[r][s] A_r
  * (coef = device [n_rel][n_slices], the basis coefficients: any n_rel); the ROOT term's slice
  * follows, and `weight` is [f_out_pad][(n_slices + ROOT terms) * f_in_pad].
- * REL plans run on the multi-kernel path only: the rows, fused and wide paths decline them. */
+ * REL plans run on the multi-kernel path only: the rows, fused and wide paths decline them.
+ * REL under edge masks (v27; plan.edge_masks = 1, mask columns are the subgraph's edges): taken
+ * when every conv layer carries agg_eid, self_ptr and self_eid (a plan that lacks one is refused
+ * before any launch).  Nodes are never masked, so every target is "on".  In row b, relation r's
+ * edge set at target t is: the CSR in-edges e of relation r with bit(b, agg_eid[e]) set,
+ * duplicates as separate entries, plus one copy of the target's own row per kept self-loop edge of
+ * type r, i.e. per column of self_eid[self_ptr[r][t] .. self_ptr[r][t + 1]) whose bit is set
+ * (self_mult is not read).  XPG_REL_MEAN divides by the relation's kept count, by 1 when that is
+ * 0; XPG_REL_SUM does not divide.  ROOT and bias are unchanged.  seg_ptr / seg_rel list the
+ * relations with an in-edge or a self-loop in the unmasked subgraph.  Still no degree pass and no
+ * degree region in the workspace; still the multi-kernel path only. */
 enum xpg_rel_norm { XPG_REL_MEAN = 0, XPG_REL_SUM = 1 };
 
 int xpg_abi_version(void);
@@ -360,6 +372,11 @@ typedef struct xpg_forward_plan {
   int32_t edge_dot;        /* 0: per-target outputs (default), 1: dot-product decoder   */
   int32_t dot_a, dot_b;    /* target positions in the last frontier                   */
   int32_t dot_act;         /* enum xpg_act applied to the dot product                  */
+  /* v27, edge_dot only: NULL = the plain dot product above, unchanged.  Non-NULL: device [n_real]
+   * per-column scale d (a DistMult decoder's relation embedding of the plan's query edge type,
+   * fixed per plan): y[r] = act(sum_f (h_a[f] * d[f]) * h_b[f]), s = fmaf(h_a[f] * d[f], h_b[f], s)
+   * in column order. */
+  const float* dot_scale;
 } xpg_forward_plan;
 
 /* Workspace needed by xpg_masked_forward for `rows` mask rows. */
