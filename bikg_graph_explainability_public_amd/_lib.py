@@ -17,6 +17,7 @@ MAX_TERMS = 8
 ACT = {None: 0, "identity": 0, "relu": 1, "sigmoid": 2, "tanh": 3, "leaky_relu": 4, "elu": 5}
 TERM = {"gcn": 0, "mean": 1, "root": 2, "att": 3, "sum": 4, "max": 5, "rel": 6}
 REL_NORM = {"mean": 0, "sum": 1}
+POOL = {None: 0, "mean": 1, "sum": 2, "max": 3}
 
 c_i32, c_i64, c_f32, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -45,7 +46,7 @@ class LayerDesc(ctypes.Structure):
                 ("terms", TermDesc * MAX_TERMS), ("weight", c_vp), ("bias", c_vp),
                 ("tgt_type", c_vp), ("n_types", c_i32),
                 ("agg_eid", c_vp), ("self_ptr", c_vp), ("self_eid", c_vp),
-                ("seg_ptr", c_vp), ("seg_rel", c_vp)]
+                ("seg_ptr", c_vp), ("seg_rel", c_vp), ("pool", c_i32)]
 
 
 class HeadDesc(ctypes.Structure):
@@ -102,6 +103,9 @@ _SIGS = {
     "xpg_forward_describe": ([ctypes.POINTER(ForwardPlanDesc), c_i64, ctypes.c_char_p,
                               ctypes.c_size_t], c_i32),
     "xpg_wide_variants": ([ctypes.c_char_p, ctypes.c_size_t], c_i32),
+    "xpg_pool_workspace": ([c_i64, c_i64, c_i64, ctypes.POINTER(ctypes.c_size_t)], c_i32),
+    "xpg_pool_rows": ([c_vp, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp, ctypes.c_size_t, c_vp], c_i32),
+    "xpg_pool_describe": ([c_i64, c_i64, c_i64, c_i32, ctypes.c_char_p, ctypes.c_size_t], c_i32),
     "xpg_profile_enable": ([ctypes.c_int], c_i32),
     "xpg_profile_read": ([c_vp, c_vp, c_i32], c_i32),
     "xpg_wlm_workspace": ([c_i64, c_i64, c_i64, c_i64, ctypes.POINTER(ctypes.c_size_t)], c_i32),
@@ -143,7 +147,12 @@ def load(path=None):
     except OSError as e:  # pragma: no cover
         raise NativeLibraryError(f"failed to load {path}: {e}") from e
     for name, (args, res) in _SIGS.items():
-        fn = getattr(lib, name)
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise NativeLibraryError(
+                f"{path} does not export {name}: a stale build of an older source tree "
+                "(run __graft_entry__.build())") from e
         fn.argtypes = args
         fn.restype = res
     if lib.xpg_abi_version() != ABI_VERSION:

@@ -6001,8 +6001,178 @@ __global__ void k_argmin_first(const double* __restrict__ v, int64_t n, int32_t*
   *out = bi;
 }
 
+// ------------------------------------------------------------------------------------ readout
+// Graph-level readout (xpg_layer_desc.pool, xpg_pool_rows; the rules are in xpgnn.h): h
+// [rows][n][ld] -> one row of ld floats per mask row.  Grid (parts, rows): part p reduces the node
+// rows [p * kPoolPartNodes, ...) of its mask row.  Lanes are the row's float4 chunks (ld / 4 <= 64);
+// when fewer than 64, the wave's further lane groups take further node rows (a chunk count that
+// does not divide 64, e.g. 24 at ld = 96, leaves the last lanes idle: they load nothing).  Slot
+// (wave, group) strides over the part's node rows, kPoolUnroll 16-byte loads in flight before the
+// first add / max; the slots then combine through LDS in slot order.  Every output is a fixed-order
+// reduction that depends on (n, ld) alone: no atomics, nothing depends on rows or timing.
+constexpr int kPoolWaves = 4;
+constexpr int kPoolPartNodes = 512;  // node rows per workgroup: 128 per wave at ld = 256
+constexpr int kPoolUnroll = 4;
+
+template <int KIND>
+__device__ __forceinline__ float4 pool_identity() {
+  if (KIND == XPG_POOL_MAX) {
+    const float ninf = -__builtin_huge_valf();
+    return make_float4(ninf, ninf, ninf, ninf);
+  }
+  return make_float4(0.f, 0.f, 0.f, 0.f);
+}
+template <int KIND>
+__device__ __forceinline__ void pool_op(float4& a, const float4 v) {
+  if (KIND == XPG_POOL_MAX) {
+    a.x = fmaxf(a.x, v.x); a.y = fmaxf(a.y, v.y); a.z = fmaxf(a.z, v.z); a.w = fmaxf(a.w, v.w);
+  } else {
+    a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+  }
+}
+__device__ __forceinline__ float4 pool_div(const float4 a, float d) {
+  return make_float4(a.x / d, a.y / d, a.z / d, a.w / d);
+}
+
+// out: [rows][gridDim.x][ld] (the partial rows; with one part, the output rows themselves, and
+// MEAN divides here)
+template <int KIND>
+__global__ __launch_bounds__(64 * kPoolWaves) void k_pool(const float* __restrict__ h, int n, int ld,
+                                                          float* __restrict__ out) {
+  __shared__ float4 red[64 * kPoolWaves];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int chunks = ld >> 2;
+  const int groups = 64 / chunks;
+  const int g = lane / chunks, c = lane - g * chunks;
+  const int slots = kPoolWaves * groups;
+  const int64_t row = blockIdx.y;
+  const int lo = blockIdx.x * kPoolPartNodes;
+  const int hi = min(n, lo + kPoolPartNodes);
+  float4 acc = pool_identity<KIND>();
+  if (g < groups) {
+    const float4* base = reinterpret_cast<const float4*>(h + row * (int64_t)n * ld) + c;
+    int i = lo + wave * groups + g;
+    for (; i + (kPoolUnroll - 1) * slots < hi; i += kPoolUnroll * slots) {
+      float4 v[kPoolUnroll];
+#pragma unroll
+      for (int q = 0; q < kPoolUnroll; ++q) v[q] = base[(int64_t)(i + q * slots) * chunks];
+#pragma unroll
+      for (int q = 0; q < kPoolUnroll; ++q) pool_op<KIND>(acc, v[q]);
+    }
+    for (; i < hi; i += slots) pool_op<KIND>(acc, base[(int64_t)i * chunks]);
+  }
+  red[threadIdx.x] = acc;  // a slot without a node row holds the identity
+  __syncthreads();
+  if (threadIdx.x < chunks) {
+    float4 r = red[threadIdx.x];
+    for (int s = 1; s < slots; ++s) {
+      const int w = s / groups, gg = s - w * groups;
+      pool_op<KIND>(r, red[w * 64 + gg * chunks + threadIdx.x]);
+    }
+    if (KIND == XPG_POOL_MEAN && gridDim.x == 1) r = pool_div(r, static_cast<float>(n));
+    reinterpret_cast<float4*>(out + (row * gridDim.x + blockIdx.x) * (int64_t)ld)[threadIdx.x] = r;
+  }
+}
+
+// part [rows][parts][ld] -> out [rows][ld], parts combined in ascending order; MEAN divides here
+template <int KIND>
+__global__ __launch_bounds__(64) void k_pool_finish(const float* __restrict__ part, int parts, int n, int ld,
+                                                    float* __restrict__ out) {
+  const int chunks = ld >> 2, c = threadIdx.x;
+  if (c >= chunks) return;
+  const int64_t row = blockIdx.x;
+  const float4* base = reinterpret_cast<const float4*>(part + row * (int64_t)parts * ld) + c;
+  float4 r = base[0];
+  int p = 1;
+  for (; p + kPoolUnroll <= parts; p += kPoolUnroll) {
+    float4 v[kPoolUnroll];
+#pragma unroll
+    for (int q = 0; q < kPoolUnroll; ++q) v[q] = base[(int64_t)(p + q) * chunks];
+#pragma unroll
+    for (int q = 0; q < kPoolUnroll; ++q) pool_op<KIND>(r, v[q]);
+  }
+  for (; p < parts; ++p) pool_op<KIND>(r, base[(int64_t)p * chunks]);
+  if (KIND == XPG_POOL_MEAN) r = pool_div(r, static_cast<float>(n));
+  reinterpret_cast<float4*>(out + row * (int64_t)ld)[c] = r;
+}
+
+// The one selection behind launch_pool and xpg_pool_describe: parts depends on n only.
+struct PoolPick {
+  int parts;
+  const char* name;  // the kernel(s) by template argument
+};
+int pool_pick(int64_t rows, int64_t n, int64_t ld, int kind, PoolPick* p) {
+  XPG_REQ(kind >= XPG_POOL_MEAN && kind <= XPG_POOL_MAX, "pool: kind outside enum xpg_pool");
+  XPG_REQ(rows >= 0 && n >= 1 && n <= INT32_MAX - 4 * kPoolPartNodes, "pool: rows >= 0 and 1 <= n < 2^31 required");
+  XPG_REQ(ld >= 4 && ld <= 256 && ld % 4 == 0, "pool: ld must be a multiple of 4 in 4..256");
+  p->parts = static_cast<int>(cdiv(n, kPoolPartNodes));
+  static const char* const one[] = {"k_pool<mean>", "k_pool<sum>", "k_pool<max>"};
+  static const char* const two[] = {"k_pool<mean>+k_pool_finish<mean>", "k_pool<sum>+k_pool_finish<sum>",
+                                    "k_pool<max>+k_pool_finish<max>"};
+  p->name = (p->parts == 1 ? one : two)[kind - XPG_POOL_MEAN];
+  return XPG_OK;
+}
+size_t pool_partial_bytes(int64_t rows, int parts, int64_t ld) {
+  return parts > 1 ? sizeof(float) * (size_t)rows * parts * ld : 0;
+}
+
+int launch_pool(const float* h, int64_t rows, int64_t n, int64_t ld, int kind, float* out, void* ws, size_t ws_bytes,
+                hipStream_t st) {
+  PoolPick pick;
+  if (const int rc = pool_pick(rows, n, ld, kind, &pick)) return rc;
+  if (rows == 0) return XPG_OK;
+  XPG_REQ(h && out, "pool: null input or output");
+  XPG_REQ(reinterpret_cast<uintptr_t>(h) % 16 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0,
+          "pool: h and out must be 16-byte aligned");
+  const int parts = pick.parts;
+  float* part = out;
+  if (parts > 1) {
+    XPG_REQ(ws && ws_bytes >= pool_partial_bytes(rows, parts, ld), "pool: workspace too small");
+    XPG_REQ(reinterpret_cast<uintptr_t>(ws) % 16 == 0, "pool: workspace must be 16-byte aligned");
+    part = static_cast<float*>(ws);
+  }
+  const int ni = static_cast<int>(n), ldi = static_cast<int>(ld);
+  for (int64_t r0 = 0; r0 < rows; r0 += 65535) {  // grid.y limit; a row's result does not depend on it
+    const unsigned nr = static_cast<unsigned>(std::min<int64_t>(65535, rows - r0));
+    const float* hr = h + r0 * n * ld;
+    float* pr = part + r0 * parts * ld;
+    float* orow = out + r0 * ld;
+    const dim3 grid(static_cast<unsigned>(parts), nr), block(64 * kPoolWaves);
+    switch (kind) {
+#define XPG_POOL_CASE(K)                                                                          \
+  case K:                                                                                         \
+    hipLaunchKernelGGL(k_pool<K>, grid, block, 0, st, hr, ni, ldi, pr);                           \
+    if (parts > 1) hipLaunchKernelGGL(k_pool_finish<K>, dim3(nr), dim3(64), 0, st, pr, parts, ni, ldi, orow); \
+    break;
+      XPG_POOL_CASE(XPG_POOL_MEAN)
+      XPG_POOL_CASE(XPG_POOL_SUM)
+      XPG_POOL_CASE(XPG_POOL_MAX)
+#undef XPG_POOL_CASE
+    }
+    XPG_LAUNCHED();
+  }
+  return XPG_OK;
+}
+
 // ------------------------------------------------------------------------------------ helpers
 size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
+
+// pooled plans (xpg_layer_desc.pool on the last conv layer) run on the multi-kernel path only
+int plan_pool(const xpg_forward_plan* p) { return p->layers[p->n_layers - 1].pool; }
+// the host checks of a pooled plan (xpgnn.h, enum xpg_pool): before any launch
+int pool_plan_check(const xpg_forward_plan* p) {
+  XPG_REQ(p->layers != nullptr, "plan: no layers");
+  for (int l = 0; l + 1 < p->n_layers; ++l)
+    XPG_REQ(p->layers[l].pool == 0, "masked_forward: pool on a layer that is not the last conv layer");
+  const int pool = plan_pool(p);
+  if (pool == 0) return XPG_OK;
+  XPG_REQ(pool >= XPG_POOL_MEAN && pool <= XPG_POOL_MAX, "masked_forward: pool outside enum xpg_pool");
+  XPG_REQ(!p->edge_masks, "masked_forward: pool does not take edge-mask plans (edge_masks)");
+  XPG_REQ(!p->edge_dot, "masked_forward: pool does not take a link decoder (edge_dot)");
+  for (int l = 0; l < p->n_layers; ++l)
+    XPG_REQ(p->layers[l].tgt_type == nullptr, "masked_forward: pool does not take multi-node-type plans (tgt_type)");
+  return XPG_OK;
+}
 
 // node-type-gated terms (multi-node-type HeteroConv) run on the multi-kernel path only
 bool plan_multi_type(const xpg_forward_plan* p) {
@@ -6085,10 +6255,12 @@ int deg_pitch(const xpg_forward_plan* p) {
 struct WsLayout {
   size_t kin = 0, agg = 0, head0 = 0, head1 = 0, score = 0, ctl = 0, total = 0;
   size_t h[64];
+  size_t pool = 0, pool_part = 0, pool_part_bytes = 0;  // pooled plans only: the region after ctl
 };
 
 int layout_ws(const xpg_forward_plan* p, int64_t rows, WsLayout* L) {
   XPG_REQ(p && p->n_layers >= 1 && p->n_layers <= 64, "plan: 1..64 conv layers required");
+  if (const int rc = pool_plan_check(p)) return rc;
   size_t off = 0;
   L->kin = off;  // REL plans read no degrees: no region (n_rel can be in the hundreds)
   if (!plan_has_rel(p)) off += align_up(sizeof(float) * (size_t)rows * p->n_rel * deg_pitch(p));
@@ -6122,6 +6294,16 @@ int layout_ws(const xpg_forward_plan* p, int64_t rows, WsLayout* L) {
   off += align_up(score_max);
   L->ctl = off;  // the rows forward's block-scheduling counters (zeroed before each launch)
   off += align_up(sizeof(int) * 32);
+  if (plan_pool(p)) {  // the pooled rows, then the partial rows of a split readout
+    const xpg_layer_desc& last = p->layers[p->n_layers - 1];
+    PoolPick pick;
+    if (const int rc = pool_pick(rows, last.n_tgt, last.f_out_pad, last.pool, &pick)) return rc;
+    L->pool = off;
+    off += align_up(sizeof(float) * (size_t)rows * last.f_out_pad);
+    L->pool_part = off;
+    L->pool_part_bytes = pool_partial_bytes(rows, pick.parts, last.f_out_pad);
+    off += align_up(L->pool_part_bytes);
+  }
   L->total = off;
   return XPG_OK;
 }
@@ -6397,6 +6579,7 @@ int try_fused_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t r
   if (plan_has_attention(p)) return 1;  // attention: multi-kernel path only
   if (plan_has_rel(p)) return 1;        // typed relations (REL): multi-kernel path only
   if (plan_sum_max_raw(p)) return 1;    // SUM / MAX terms, raw layer 1: not in this kernel
+  if (plan_pool(p)) return 1;           // pooled plans (readout): multi-kernel path only
   if (p->n_layers > kFusedMaxLayers || p->n_head > kFusedMaxHead || plan_multi_type(p)) return 1;
   if (p->edge_masks || p->edge_dot) return 1;  // edge problems: multi-kernel path only
   FusedArgs a;
@@ -6671,6 +6854,7 @@ bool wide_wanted(const xpg_forward_plan* p) {
   if (plan_has_attention(p)) return false;          // attention: multi-kernel path only
   if (plan_has_rel(p)) return false;                // typed relations (REL): multi-kernel path only
   if (plan_sum_max_raw(p)) return false;            // SUM / MAX terms, raw layer 1: not in the wide kernels
+  if (plan_pool(p)) return false;                   // pooled plans (readout): multi-kernel path only
   if (forward_is("wide")) return true;
   if (forward_is(nullptr)) return false;  // another path forced
   return p->n_layers == 2 && p->layers[0].n_tgt >= 8192;
@@ -6967,6 +7151,7 @@ int try_rows_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t ro
   if (p->edge_masks || p->edge_dot) return 1;  // edge problems: multi-kernel path only
   if (plan_has_attention(p)) return 1;         // attention: multi-kernel path only
   if (plan_has_rel(p)) return 1;               // typed relations (REL): multi-kernel path only
+  if (plan_pool(p)) return 1;                  // pooled plans (readout): multi-kernel path only
   // SUM runs here (MEAN with inv = 1); MAX fits no per-edge coefficient and a raw layer 1 has no tables
   if (plan_has_kind(p, XPG_TERM_MAX) || plan_raw_l1(p)) return 1;
   RowsFwdArgs a;
@@ -7621,6 +7806,31 @@ int xpg_wide_variants(char* buf, size_t n) {
   return XPG_OK;
 }
 
+int xpg_pool_workspace(int64_t rows, int64_t n, int64_t ld, size_t* bytes) {
+  XPG_REQ(bytes != nullptr, "pool_workspace: no output");
+  PoolPick pick;
+  if (const int rc = pool_pick(rows, n, ld, XPG_POOL_SUM, &pick)) return rc;
+  *bytes = pool_partial_bytes(rows, pick.parts, ld);
+  return XPG_OK;
+}
+
+int xpg_pool_rows(const float* h, int64_t rows, int64_t n, int64_t ld, int32_t kind, float* out, void* workspace,
+                  size_t workspace_bytes, xpg_stream_t stream) {
+  return launch_pool(h, rows, n, ld, kind, out, workspace, workspace_bytes, S(stream));
+}
+
+int xpg_pool_describe(int64_t rows, int64_t n, int64_t ld, int32_t kind, char* buf, size_t nbytes) {
+  XPG_REQ(buf != nullptr && nbytes > 0, "pool_describe: no buffer");
+  buf[0] = 0;
+  PoolPick pick;
+  if (const int rc = pool_pick(rows, n, ld, kind, &pick)) return rc;
+  const std::string s = std::string(pick.name) + " parts=" + std::to_string(pick.parts) +
+                        " part_nodes=" + std::to_string(kPoolPartNodes);
+  if (s.size() + 1 > nbytes) return fail(XPG_ENOSPC, "pool_describe: buffer too small");
+  std::memcpy(buf, s.c_str(), s.size() + 1);
+  return XPG_OK;
+}
+
 int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t rows, float* y,
                        void* workspace, size_t workspace_bytes, xpg_stream_t stream) {
   WsLayout L;
@@ -7658,7 +7868,10 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
   // past the first) and no link decoder: no 32-wide padded head tile, no column pick.
   OutColumn fh;
   bool fuse_out = false;
-  if (!p->edge_dot && p->n_head >= 1 && (p->n_head >= 2 || p->n_layers >= 2)) {
+  // A pooled plan's head follows the readout, which is no dense layer: its last head layer is
+  // fused only into the head layer before it (k_dense HEAD on M = rows rows, as for one query).
+  const int pool = plan_pool(p);
+  if (!p->edge_dot && p->n_head >= 1 && (p->n_head >= 2 || (p->n_layers >= 2 && !pool))) {
     const xpg_head_desc& hl = p->head[p->n_head - 1];
     const int64_t prev_pad = p->n_head >= 2 ? p->head[p->n_head - 2].n_pad : p->layers[p->n_layers - 1].f_out_pad;
     if (hl.k_pad == prev_pad && p->out_col >= 0 && p->out_col < hl.n_real) {
@@ -7809,9 +8022,16 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
     }
   }
   const xpg_layer_desc& last = p->layers[p->n_layers - 1];
-  const int64_t M = rows * last.n_tgt;
+  int64_t M = rows * last.n_tgt;
   const float* cur = reinterpret_cast<const float*>(ws + L.h[p->n_layers - 1]);
   int64_t cur_ld = last.f_out_pad;
+  if (pool) {  // the readout: each mask row's n_tgt rows -> one row; the head then runs on `rows` rows
+    float* pooled = reinterpret_cast<float*>(ws + L.pool);
+    rc = launch_pool(cur, rows, last.n_tgt, last.f_out_pad, pool, pooled, ws + L.pool_part, L.pool_part_bytes, st);
+    if (rc) return rc;
+    M = rows;
+    cur = pooled;
+  }
   const int n_head_launch = p->n_head - (fuse_out ? 1 : 0);  // the last head layer fused (fh)
   for (int i = 0; i < n_head_launch; ++i) {
     const xpg_head_desc& hd = p->head[i];

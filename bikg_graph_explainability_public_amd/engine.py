@@ -512,6 +512,46 @@ def wide_variants():
     return buf.value.decode().split()
 
 
+# ----------------------------------------------------------------------------- readout
+def pool_describe(rows: int, n: int, ld: int, kind: str) -> str:
+    """The kernel(s) the readout launches for h [rows, n, ld] (xpg_pool_describe, a host query
+    sharing the launcher's selection): `k_pool<KIND> parts=1 part_nodes=P`, or
+    `k_pool<KIND>+k_pool_finish<KIND> parts=N part_nodes=P` when a row is split (n > P)."""
+    buf = ctypes.create_string_buffer(128)
+    _lib.check(_lib.load().xpg_pool_describe(int(rows), int(n), int(ld), _lib.POOL[kind], buf, len(buf)))
+    return buf.value.decode()
+
+
+def pool_workspace_bytes(rows: int, n: int, ld: int) -> int:
+    nb = ctypes.c_size_t(0)
+    _lib.check(_lib.load().xpg_pool_workspace(int(rows), int(n), int(ld), ctypes.byref(nb)))
+    return nb.value
+
+
+def pool_rows(h: torch.Tensor, kind: str, out: torch.Tensor = None,
+              workspace: torch.Tensor = None) -> torch.Tensor:
+    """Graph-level readout of h [rows, n, ld] fp32 (ld % 4 == 0, at most 256) -> [rows, ld]:
+    column-wise "mean" / "sum" / "max" over each row's n node rows (xpg_pool_rows; the readout of
+    a pooled ForwardPlan on its own).  Deterministic: a fixed reduction order that depends on
+    (n, ld) only.  `out` / `workspace` (uint8, pool_workspace_bytes): caller-owned buffers."""
+    _lib.require_device(h, "h")
+    if h.dtype != torch.float32 or h.dim() != 3 or not h.is_contiguous():
+        raise ValueError("h must be a contiguous float32 [rows, n, ld] tensor")
+    rows, n, ld = h.shape
+    if out is None:
+        out = torch.empty((rows, ld), dtype=torch.float32, device=h.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (rows, ld) or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 [rows, ld] tensor")
+    need = pool_workspace_bytes(rows, n, ld)
+    if workspace is None:
+        workspace = _workspace(h.device, need) if need else None
+    elif workspace.dtype != torch.uint8 or workspace.numel() < need:
+        raise ValueError("workspace must be a uint8 device tensor of pool_workspace_bytes")
+    call("xpg_pool_rows", ptr(h), rows, n, ld, _lib.POOL[kind], ptr(out), ptr(workspace),
+         workspace.numel() if workspace is not None else 0, _lib.stream_of(h.device))
+    return out
+
+
 # ----------------------------------------------------------------------------- forward plan
 def plan_arrays(S, rel_np, queries, L, rel_eid=None):
     """Receptive-field frontiers and CSR arrays of a ForwardPlan, built on the host by the
@@ -720,7 +760,12 @@ class ForwardPlan:
         queries a and b instead of one column per query; `link` = (a, b, act, d) with a vector d
         of the output width scales the columns, act(sum_f h_a[f] d[f] h_b[f]) (DistMult, d = the
         query relation's embedding).  A typed-relation ("rel") program takes one entry of
-        `rel_edges` / `edge_cols` per edge type."""
+        `rel_edges` / `edge_cols` per edge type.
+
+        A pooled program (`program.pool`, nn.PooledModel): after the last conv layer the rows of
+        the `queries` (pipeline.build_plan passes every node) reduce to one row per mask row
+        (xpg_layer_desc.pool), the head runs on it and forward returns [rows, 1]; node masks,
+        single-node-type programs only."""
         device = torch.device(device) if device is not None else sub_feat.device
         _lib.require_device(torch.empty(0, device=device), "plan device")
         if len(program.convs) == 0:
@@ -742,6 +787,16 @@ class ForwardPlan:
                 raise ValueError("edge_cols must give one mask column per edge of every relation")
             if program.n_types > 1:
                 raise ValueError("edge masks on multi-node-type programs are not supported")
+        self.pool = getattr(program, "pool", None)
+        if self.pool is not None:
+            # graph-level readout after the last conv layer (xpgnn.h, enum xpg_pool): one output
+            # per mask row over the plan's last frontier (pipeline.build_plan: every node)
+            if self.pool not in _lib.POOL:
+                raise ValueError(f"unknown pool {self.pool!r}")
+            if rel_eid is not None or link is not None:
+                raise ValueError("pooled (graph-level) programs on edge-mask plans are not supported")
+            if program.n_types > 1:
+                raise ValueError("pooled (graph-level) multi-node-type programs are not supported")
         self.edge_masks = rel_eid is not None
         self.cols = (int(max((int(c.max()) for c in rel_eid if c.size), default=-1)) + 1
                      if self.edge_masks else S)
@@ -962,6 +1017,8 @@ class ForwardPlan:
                 self._keep.append(Wc)
                 ld.weight = Wc.data_ptr()
             prev_pad = f_out_pad
+        if self.pool is not None:
+            self._layers[L - 1].pool = _lib.POOL[self.pool]
 
         self._head = (HeadDesc * max(1, len(program.head)))()
         for i, h in enumerate(program.head):
@@ -1014,6 +1071,8 @@ class ForwardPlan:
                 self._keep.append(dp)
                 self.desc.dot_scale = dp.data_ptr()
             self.n_out = 1
+        if self.pool is not None:
+            self.n_out = 1  # forward returns [rows, 1], as link plans do
         self._upload_i32()
         self._ws = None
         self._ws_stream = None  # raw handle of the stream that last used self._ws

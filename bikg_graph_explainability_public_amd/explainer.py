@@ -25,6 +25,7 @@ from .data import Data
 from .masks import Mask, dataloader_seed_draw
 from .model import Model
 from .pathways import Pathways
+from .program import POOL_KIND
 from .wlm import LinearRegression
 
 
@@ -90,6 +91,24 @@ class Explainer:
         self.group = None     # torch.distributed process group for multi-GPU runs (None = world)
         self._verified = set()  # module states whose compiled program passed verify_plan
         self._queries = {}      # per-query (prepare context, plan, arch check): _query_key
+        if self.pooled:
+            if "graph" not in self.problem:
+                raise ValueError(f"arch.forward takes three parameters (x, edge_index, batch): that "
+                                 f"form is called as a graph-level (pooled) model, with one output "
+                                 f"per graph and none per node or edge, so problem={problem!r} "
+                                 "cannot select one; use problem='graph_prediction'")
+            if bool(self.params.get("edge_masks", False)):
+                raise ValueError("arch.forward takes three parameters (x, edge_index, batch): that "
+                                 "form is a graph-level (pooled) model, explained over node masks; "
+                                 "params['edge_masks'] is not supported with it")
+
+    @property
+    def pooled(self):
+        """The arch is a graph-level model (a forward of (x, edge_index, batch), nn.PooledModel):
+        conv stack, global mean / add / max readout, MLP.  `graph_prediction` then explains the
+        graph's own prediction, one output per perturbed copy.  `element` is still validated
+        against `names` as the reference validates it, and selects nothing."""
+        return pipeline.pooled_call(self.arch)
 
     @property
     def attention_engine(self):
@@ -289,7 +308,10 @@ class Explainer:
     # ------------------------------------------------------------------------------ run
     def prepare(self, element, device):
         """Host orchestration of explainer.py:345-480 (no RNG consumed): heterogeneous
-        flattening, computational subgraph, community filtering.  Returns a dict context."""
+        flattening, computational subgraph, community filtering.  Returns a dict context.
+        With a pooled (graph-level) arch under graph_prediction nothing changes here: `element` is
+        still validated against `names` as the reference validates it, and then selects nothing,
+        since each perturbed copy of the graph has exactly one output."""
         feat, ei = _to_device(self.feat, device), _to_device(self.edge_index, device)
         raw = Data(feat, ei)
         pw_raw = Pathways(self.pathways, self.pathway_names) if self.pathways is not None else None
@@ -613,7 +635,10 @@ class Explainer:
         self.last_run = {"engine": plan is not None, "repeats": diag, "S": S,
                          "sub_ind": sub_ind, "plan": plan, "weights": w.unbind(0),
                          "phases": clock, "arch_check": arch_check,
-                         "query_cache": "off" if qkey is None else "hit" if hit else "miss"}
+                         "query_cache": "off" if qkey is None else "hit" if hit else "miss",
+                         # graph-level readout of a pooled arch ("mean" | "sum" | "max"), else None
+                         "pool": plan.pool if plan is not None else
+                         (POOL_KIND.get(getattr(self.arch, "pool", None)) if self.pooled else None)}
         return config_val_df, pathway_df
 
     def run_queries(self, elements, times=1):
@@ -634,6 +659,9 @@ class Explainer:
         single-node-type archs only."""
         assert "graph" in self.problem, \
             "run_queries shares one mask set across queries: graph_prediction problems only"
+        if self.pooled:
+            raise ValueError("run_queries: a pooled (graph-level) arch has one output per graph, "
+                             "nothing to share between queries; use run")
         if not torch.cuda.is_available():
             raise _lib.NativeLibraryError("Explainer.run_queries needs an MI355X (HIP) device; "
                                           "there is no CPU fallback")

@@ -24,15 +24,21 @@ class Model:
             hops //= num_relations
         return hops
 
-    def infer(self, feat, edge_index, node_types=None, edge_types=None):
-        """model.py:62-116 — call convention picked from the forward signature."""
-        nargs = len(inspect.signature(self.arch.forward).parameters)
+    def infer(self, feat, edge_index, node_types=None, edge_types=None, batch=None):
+        """model.py:62-116 — call convention picked from the forward signature.  A forward of
+        three parameters is a graph-level (pooled) model, called `arch(x, edge_index, batch)`:
+        `batch` [n] gives each node's graph (the copy of the union graph it belongs to; None: one
+        graph).  An edge-level model's (x, edge_index, edge_label_index) is not that form."""
+        names = list(inspect.signature(self.arch.forward).parameters)
+        nargs = len(names)
         with torch.no_grad():
             if nargs == 2:
                 return self.arch(feat, edge_index)
+            if nargs == 3 and names[2] != "edge_label_index":
+                return self.arch(feat, edge_index, batch)
             if nargs == 4 and node_types is not None and edge_types is not None:
                 return self.arch(feat, edge_index, node_types, edge_types)
-        raise TypeError("arch.forward must take (x, edge_index) or "
+        raise TypeError("arch.forward must take (x, edge_index), (x, edge_index, batch) or "
                         "(x, edge_index, node_types, edge_types)")
 
     def predict_hetero_output(self, feat, edge_index, node_types, edge_types, node_type_names,

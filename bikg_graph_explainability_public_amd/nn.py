@@ -15,6 +15,8 @@ import torch
 from torch import nn
 import torch.nn.functional as F
 
+from .program import POOL_KIND as _POOLS  # readout names: "add" is "sum"
+
 
 class MessagePassing(nn.Module):
     """Marker base class: `Model.get_hops` counts instances (PyG get_num_hops semantics)."""
@@ -619,3 +621,66 @@ class RelLinkModel(nn.Module):
             s = s * self.rel_emb[elt.reshape(-1).long()]
         s = (s * z[eli[1].long()]).sum(-1, keepdim=True)
         return torch.sigmoid(s) if self.act == "sigmoid" else s
+
+
+def global_pool(h, batch, kind, size=None):
+    """Graph-level readout (PyG global_mean_pool / global_add_pool / global_max_pool): the rows of
+    `h` [n, C] reduced per graph, `batch` [n] giving each row's graph (None: one graph), to
+    [size, C] (`size` default: batch.max() + 1).  Plain torch: index_add_ for the sums (mean = sum /
+    count) and scatter_reduce(..., "amax", include_self=False) for max; a graph without a node
+    gives 0."""
+    if kind not in _POOLS:
+        raise ValueError(f"unknown pool {kind!r}: one of {sorted(_POOLS)}")
+    kind = _POOLS[kind]
+    if batch is None:
+        batch = torch.zeros(h.shape[0], dtype=torch.long, device=h.device)
+    batch = batch.reshape(-1).long()
+    if size is None:
+        size = int(batch.max()) + 1 if batch.numel() else 1
+    if kind == "max":
+        out = torch.zeros((size, h.shape[1]), dtype=h.dtype, device=h.device)
+        return out.scatter_reduce(0, batch[:, None].expand(-1, h.shape[1]), h, "amax",
+                                  include_self=False)
+    out = torch.zeros((size, h.shape[1]), dtype=h.dtype, device=h.device).index_add_(0, batch, h)
+    if kind == "mean":
+        cnt = torch.zeros(size, dtype=h.dtype, device=h.device).index_add_(
+            0, batch, torch.ones(batch.numel(), dtype=h.dtype, device=h.device))
+        out = out / cnt.clamp(min=1)[:, None]
+    return out
+
+
+class PooledModel(nn.Module):
+    """Graph-level model (graph classifier / regressor): a node encoder, a global readout and an
+    MLP head, out = fc(pool(encoder(x, edge_index), batch)) -> [n_graphs, fc_dims[-1]].
+
+    `encoder`: a module whose leaf units follow the `[conv act?]+` rule with no Linear after them,
+    e.g. ConvStack(kind, dims, [dims[-1]]) (an empty `fc`).  `pool` in {"mean", "add", "sum",
+    "max"}; `fc` = ModuleList[Linear, act]* as in ConvStack.  forward(x, edge_index, batch=None):
+    `batch` [n] is each node's graph (None: one graph); the explainer passes it to keep the B
+    perturbed copies of the union graph apart.
+
+    The engine lowers this family by class name plus the attributes `encoder`, `pool` and `fc`
+    (program.compile_arch, as LinkModel is matched): a model that calls PyG's functional
+    global_mean_pool / global_add_pool / global_max_pool in its own forward is explained on the
+    engine by wrapping its encoder and head in this class."""
+
+    def __init__(self, encoder, pool, fc_dims, final_act="sigmoid"):
+        super().__init__()
+        if pool not in _POOLS:
+            raise ValueError(f"PooledModel pool must be one of {sorted(_POOLS)}")
+        self.encoder = encoder
+        self.pool = pool
+        fcs = []
+        for i in range(len(fc_dims) - 1):
+            fcs.append(Linear(fc_dims[i], fc_dims[i + 1]))
+            last = i == len(fc_dims) - 2
+            fcs.append((nn.Sigmoid() if final_act == "sigmoid" else nn.Identity()) if last
+                       else nn.ReLU())
+        self.fc = nn.ModuleList(fcs)
+
+    def forward(self, x, edge_index, batch=None):
+        h = self.encoder(x, edge_index)
+        h = global_pool(h, batch, self.pool)
+        for layer in self.fc:
+            h = layer(h)
+        return h

@@ -10,6 +10,7 @@ on the B-fold union graph built with the HIP edge-keep kernel) — still on the 
 KernelSHAP and surrogate stages unchanged.
 """
 import collections
+import inspect
 import warnings
 import weakref
 
@@ -128,6 +129,10 @@ def build_plan(arch, feat, edge_index, queries, node_type=None, edge_type=None,
                          "and params['edge_masks'] = True")
     x = feat
     nt = None
+    if prog.pool is not None:
+        # graph-level readout: every node is a target of the last layer (every frontier is the
+        # whole graph), the plan has one output per mask row and `queries` selects nothing
+        queries = range(feat.shape[0])
     if multi:
         nt = node_type.long().reshape(-1)
         rows_t = torch.where(nt == prog.out_type)[0].cpu()
@@ -282,6 +287,19 @@ def multi_type_targets(y_rows, empty, batch, sub_ind, S, q4=True):
     return out
 
 
+def pooled_call(arch):
+    """True for a graph-level model: a forward of three parameters (x, edge_index, batch), the
+    form Model.infer calls with the union graph's copy index per node (nn.PooledModel)."""
+    forward = getattr(arch, "forward", None)
+    if forward is None:
+        return False
+    try:
+        names = list(inspect.signature(forward).parameters)
+    except (TypeError, ValueError):
+        return False
+    return len(names) == 3 and names[2] != "edge_label_index"
+
+
 def generic_outputs(arch, feat, edge_index, mask, element_index, problem, node_type=None,
                     edge_type=None, node_type_names=None, edge_type_names=None,
                     padded_dims=None, batch=None, q4=True):
@@ -290,7 +308,10 @@ def generic_outputs(arch, feat, edge_index, mask, element_index, problem, node_t
     reference's output[ind::S] collapse, quirk Q4, broadcast over its batch).  A list of
     element indices (single-node-type graphs) returns y [R, Q]: every query's extraction from
     the same union-graph forward."""
+    pooled = pooled_call(arch)
     if isinstance(element_index, (list, tuple)):
+        if pooled:
+            raise ValueError("a pooled (graph-level) model has one output per graph: no query list")
         return _generic_multi(arch, feat, edge_index, mask, element_index, problem, node_type,
                               edge_type, node_type_names, edge_type_names, padded_dims, batch)
     data = Data(feat, edge_index)
@@ -308,6 +329,16 @@ def generic_outputs(arch, feat, edge_index, mask, element_index, problem, node_t
                 and edge_type_names is not None and n_types < 2:
             cf = data.homo2hetero(cf, cnt, node_type_names, padded_dims)
             pei = data.homo2hetero(pei, pet, edge_type_names)
+        if pooled:
+            # graph-level model: copy b's S nodes are graph b of the union graph (no node is ever
+            # removed), one output row per copy; column out_col (0) is the regression target
+            # (cf is a dict for a single-node-type graph with type names: the device is the mask's)
+            gb = torch.arange(B, device=mb.device).repeat_interleave(S)
+            out = mc.infer(cf, pei, batch=gb)
+            if out.dim() != 2 or out.shape[0] != B:
+                raise RuntimeError(f"a pooled model must return [{B}, out], got {tuple(out.shape)}")
+            ys.append(out[:, 0].reshape(-1).float())
+            continue
         if n_types < 2:
             out = mc.infer(cf, pei, cnt, pet)
         else:

@@ -87,6 +87,9 @@ class ModelProgram:
     # ROOT-only conv layers that are the second Linear of a GINConv MLP: no message passing of
     # their own (the module's hop count, count_message_passing, does not include them)
     extra_layers: int = 0
+    # PooledModel: the convs are its encoder's, the head its `fc`; between them each graph's node
+    # rows reduce to one row ("mean" | "sum" | "max"), and the program has one output per graph
+    pool: Optional[str] = None
 
     @property
     def hops(self):
@@ -483,6 +486,67 @@ def _conv_layer_multi(conv, rel_index, node_type_names, attention=False):
     return terms, bias, f_in, f_out, first_dst
 
 
+def _head_layers(prog, units, i):
+    """Append the [Linear act?]* run of `units` starting at i to prog.head; returns the index of
+    the first unit past it."""
+    while i < len(units) and _is_linear(units[i]):
+        lin = units[i]
+        act = None
+        if i + 1 < len(units) and _act_name(units[i + 1]) is not None:
+            act = _act_name(units[i + 1])
+            i += 1
+        b = _f32(lin.bias) if getattr(lin, "bias", None) is not None else None
+        prog.head.append(HeadLayer(_f32(lin.weight), b, act))
+        i += 1
+    return i
+
+
+def _check_widths(prog):
+    """Width consistency of the conv layers and the head."""
+    prev = prog.convs[0].f_in
+    for c in prog.convs:
+        if c.f_in != prev:
+            raise UnsupportedArch("conv widths do not chain")
+        prev = c.f_out
+    for h in prog.head:
+        if h.weight.shape[1] != prev:
+            raise UnsupportedArch("head widths do not chain")
+        prev = h.weight.shape[0]
+
+
+POOL_KIND = {"mean": "mean", "add": "sum", "sum": "sum", "max": "max"}
+
+
+def _compile_pooled(arch, edge_type_names, node_type_names, attention):
+    """nn.PooledModel (matched by class name + `encoder`, `pool`, `fc`): the encoder's conv
+    layers, the readout, then the Linear / activation units of `fc` as the head."""
+    pool = arch.pool
+    if not isinstance(pool, str) or pool not in POOL_KIND:
+        raise UnsupportedArch(f"PooledModel(pool={pool!r})")
+    if node_type_names is not None and len(node_type_names) >= 2:
+        raise UnsupportedArch("PooledModel on a multi-node-type graph")
+    prog = compile_arch(arch.encoder, edge_type_names, node_type_names, attention)
+    if prog.link_act is not None:
+        raise UnsupportedArch("PooledModel over an edge-level (link) encoder")
+    if prog.pool is not None:
+        raise UnsupportedArch("PooledModel over a pooled encoder")
+    if prog.head:
+        raise UnsupportedArch("PooledModel encoder with Linear layers after its convs (a head "
+                              "belongs after the readout, in fc)")
+    if any(t.kind == "rel" for c in prog.convs for t in c.terms):
+        raise UnsupportedArch("PooledModel over RGCNConv layers (typed graphs need the "
+                              "4-argument call)")
+    if prog.n_types > 1:
+        raise UnsupportedArch("PooledModel on a multi-node-type program")
+    units = list(_leaf_units(arch.fc, attention))
+    i = _head_layers(prog, units, 0)
+    if i != len(units):
+        raise UnsupportedArch(f"unexpected module order at {type(units[i]).__name__} in PooledModel.fc")
+    _check_widths(prog)
+    prog.pool = POOL_KIND[pool]
+    return prog
+
+
 def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
                  attention=False) -> ModelProgram:
     """Lower `arch` to a ModelProgram.  `edge_type_names` (list of (src, rel, dst) tuples in
@@ -492,6 +556,8 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
     arch with GATConv raises UnsupportedArch."""
     if type(arch).__name__ == "LinkModel" and hasattr(arch, "encoder"):
         prog = compile_arch(arch.encoder, edge_type_names, node_type_names, attention)
+        if prog.pool is not None:
+            raise UnsupportedArch("LinkModel over a pooled encoder")
         prog.link_act = getattr(arch, "act", "identity") or "identity"
         return prog
     if type(arch).__name__ == "RelLinkModel" and hasattr(arch, "encoder"):
@@ -507,6 +573,8 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
                                       f"output of width {width}")
             prog.link_rel = _f32(emb)
         return prog
+    if type(arch).__name__ == "PooledModel" and all(hasattr(arch, a) for a in ("encoder", "pool", "fc")):
+        return _compile_pooled(arch, edge_type_names, node_type_names, attention)
     rel_index = None
     if edge_type_names is not None:
         rel_index = {tuple(et): i for i, et in enumerate(edge_type_names)}
@@ -549,27 +617,10 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
     typed = [any(t.kind == "rel" for t in c.terms) for c in prog.convs]
     if any(typed) and not all(typed):
         raise UnsupportedArch("a model mixing RGCNConv with another conv kind")
-    while i < len(units) and _is_linear(units[i]):
-        lin = units[i]
-        act = None
-        if i + 1 < len(units) and _act_name(units[i + 1]) is not None:
-            act = _act_name(units[i + 1])
-            i += 1
-        b = _f32(lin.bias) if getattr(lin, "bias", None) is not None else None
-        prog.head.append(HeadLayer(_f32(lin.weight), b, act))
-        i += 1
+    i = _head_layers(prog, units, i)
     if i != len(units):
         raise UnsupportedArch(f"unexpected module order at {type(units[i]).__name__}")
-    # width consistency
-    prev = prog.convs[0].f_in
-    for c in prog.convs:
-        if c.f_in != prev:
-            raise UnsupportedArch("conv widths do not chain")
-        prev = c.f_out
-    for h in prog.head:
-        if h.weight.shape[1] != prev:
-            raise UnsupportedArch("head widths do not chain")
-        prev = h.weight.shape[0]
+    _check_widths(prog)
     return prog
 
 

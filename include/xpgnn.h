@@ -37,6 +37,11 @@
  *                                        edge problem's Data.perturb_edge (data.py:500-554: mask
  *                                        columns are edges) and a dot-product or DistMult link
  *                                        decoder (GCN / SAGE-mean terms, or RGCN REL terms, v27)
+ *                                        (v27 addendum, no version change: xpg_layer_desc.pool
+ *                                        appended; a conv stack followed by a global mean / add /
+ *                                        max readout and a dense head, one output per mask row)
+ *   xpg_pool_rows / _workspace / _describe — the readout alone (PyG global_mean_pool /
+ *                                        global_add_pool / global_max_pool over one graph per row)
  *   xpg_forward_describe / xpg_wide_variants — none: host queries of xpg_masked_forward's own
  *                                        dispatch (path and wide-path kernels), for tests and logs
  *   xpg_sampler_describe               — none: host query of the device samplers' own dispatch (which
@@ -121,6 +126,26 @@ enum xpg_term { XPG_TERM_GCN = 0,   /* D^-1/2 (A_r + I) D^-1/2 over relation r  
  * relations with an in-edge or a self-loop in the unmasked subgraph.  Still no degree pass and no
  * degree region in the workspace; still the multi-kernel path only. */
 enum xpg_rel_norm { XPG_REL_MEAN = 0, XPG_REL_SUM = 1 };
+/* Graph-level readout (v27 addendum: xpg_layer_desc.pool, appended after seg_rel; the version and
+ * every other layout are unchanged, and a zero-filled field means what every plan meant before).
+ * `pool` may be non-zero on the LAST conv layer only.  After that layer's bias and activation the
+ * n_tgt rows of each mask row reduce column-wise to one row of f_out_pad floats (padded columns
+ * stay 0): a global mean / add / max pooling over the plan's last frontier (build it with every
+ * node of the graph as a query for a graph-level model).  Node masks never remove a node: a
+ * masked node loses its edges and keeps its own row (features are never masked), so every one of
+ * the n_tgt targets takes part in every mask row.  MEAN is the SUM divided by (float)n_tgt (one
+ * fp32 quotient); MAX has no empty case (n_tgt >= 1).  The reduction order is fixed and depends
+ * on (n_tgt, f_out_pad) only, never on rows, a row's position in the launch or timing (no float
+ * atomics): row shards and repeated calls agree bit for bit.  The head layers then run on `rows`
+ * rows and y has `rows` values, y[r] = column out_col of row r.
+ * xpg_masked_forward / xpg_forward_workspace / xpg_forward_describe fail with XPG_EINVAL before any
+ * launch for: pool on a non-last layer, pool with edge_masks, pool with edge_dot, pool with
+ * tgt_type, pool outside this enum.  The workspace of a pooled plan is that of the same plan
+ * without pool plus, at its end, the pooled rows (rows * f_out_pad floats, rounded up to 256
+ * bytes) and, when a row is split over several workgroups, the partial rows (xpg_pool_workspace
+ * bytes, rounded up to 256).  Pooled plans run on the multi-kernel path only: the rows, fused and
+ * wide paths decline them. */
+enum xpg_pool { XPG_POOL_NONE = 0, XPG_POOL_MEAN = 1, XPG_POOL_SUM = 2, XPG_POOL_MAX = 3 };
 
 int xpg_abi_version(void);
 const char* xpg_last_error(void);
@@ -338,6 +363,8 @@ typedef struct xpg_layer_desc {
   /* layers with a REL term only (v26; NULL otherwise):                                     */
   const int32_t* seg_ptr;  /* [n_tgt + 1] each target's range of seg_rel                 */
   const int32_t* seg_rel;  /* relations with an in-edge or self-loop at the target, ascending */
+  /* graph-level readout (v27 addendum; the rules are at enum xpg_pool): 0 on every layer but the last */
+  int32_t pool;            /* enum xpg_pool                                              */
 } xpg_layer_desc;
 
 typedef struct xpg_head_desc {
@@ -403,6 +430,22 @@ int xpg_forward_describe(const xpg_forward_plan* plan, int64_t rows, char* buf, 
 /* Every `l1=<kernel>` / `l2=<kernel>` token xpg_forward_describe can write for the wide path, one
  * per line (v23; the table the selection itself picks from). */
 int xpg_wide_variants(char* buf, size_t n);
+
+/* The readout of a pooled plan on its own (v27 addendum; rules at enum xpg_pool): h [rows][n][ld]
+ * fp32 -> out [rows][ld], out[r][c] = mean / sum / max over i of h[r][i][c] (kind = enum xpg_pool,
+ * not NONE).  ld % 4 == 0, 4 <= ld <= 256, n >= 1, h / out / workspace 16-byte aligned.  A row of
+ * more nodes than one workgroup reduces is split into `parts` contiguous node ranges (parts
+ * depends on n only): k_pool writes one partial row per part into the workspace
+ * ([rows][parts][ld] floats, xpg_pool_workspace bytes; 0 when parts == 1) and k_pool_finish
+ * combines them in ascending part order.  The workspace's prior contents never matter. */
+int xpg_pool_workspace(int64_t rows, int64_t n, int64_t ld, size_t* bytes);
+int xpg_pool_rows(const float* h, int64_t rows, int64_t n, int64_t ld, int32_t kind, float* out,
+                  void* workspace, size_t workspace_bytes, xpg_stream_t stream);
+/* The kernels xpg_pool_rows (and a pooled plan's readout) launches for a shape, as text, e.g.
+ * `k_pool<sum> parts=1 part_nodes=512` or `k_pool<mean>+k_pool_finish<mean> parts=3 part_nodes=512`
+ * (part_nodes = the node rows one workgroup reduces; parts = ceil(n / part_nodes)).  A HOST
+ * function sharing the launcher's selection; XPG_ENOSPC when `nbytes` do not hold the text. */
+int xpg_pool_describe(int64_t rows, int64_t n, int64_t ld, int32_t kind, char* buf, size_t nbytes);
 
 /* Optional per-kernel timing of xpg_masked_forward's wide (full-graph) path (v13): with profiling
  * on, every launch of a profiled kernel is bracketed by two hipEvents on its stream;

@@ -1,0 +1,303 @@
+"""Graph-level (pooled) models without a GPU: nn.PooledModel against the fp64 restatement of
+tests/pool_ref.py, the lowering (program.compile_arch), Model.infer's 3-parameter call, and the
+host side of the C-ABI (xpg_layer_desc.pool: dispatch, host checks, workspace; xpg_pool_describe) on
+synthetic descriptors whose device pointers are only tested for NULL.  Last, the sensitivity
+conditions of the GPU parity cases (tests/test_gpu_pool.py), asserted on the reference alone."""
+import ctypes
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import aggr_ref
+import pool_ref
+from test_dispatch_cpu import make_plan, describe
+
+from bikg_graph_explainability_public_amd import _lib, nn as xnn
+from bikg_graph_explainability_public_amd.model import Model
+from bikg_graph_explainability_public_amd.program import UnsupportedArch, compile_arch
+
+ENV = ("XPG_FORWARD", "XPG_FORWARD_STRICT", "XPG_DIAGNOSTICS")
+SAGE, GCN = ("mean", "root"), ("gcn",)
+
+
+@pytest.fixture(autouse=True)
+def _clean_env(monkeypatch):
+    for k in ENV:
+        monkeypatch.delenv(k, raising=False)
+
+
+# ------------------------------------------------------------------ module vs the restatement
+def _small(seed, S=30, E=90):
+    g = np.random.default_rng(seed)
+    ei = np.concatenate([g.integers(0, S, (2, E)), np.array([[3, 3, 5], [3, 3, 5]])], 1).astype(np.int64)
+    x = torch.randn((S, 6), generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
+    return x, ei
+
+
+@pytest.mark.parametrize("pool", ["mean", "add", "max"])
+@pytest.mark.parametrize("kind", ["gcn", "sage", "sage-max", "gin"])
+def test_module_matches_restatement_fp64(kind, pool):
+    """nn.PooledModel in fp64 against pool_ref to 1e-12: one graph (batch=None) and a 3-copy union
+    graph with a batch vector (identity head: the masks must move the output)."""
+    x, ei = _small(4)
+    torch.manual_seed(6)
+    arch = pool_ref.model(kind, pool, dims=(6, 5, 4), fc=(4, 2), final_act="identity").double()
+    ones = np.ones((1, x.shape[0]), dtype=bool)
+    with torch.no_grad():
+        got = arch(x, torch.as_tensor(ei))
+    assert tuple(got.shape) == (1, 2)
+    np.testing.assert_allclose(got.numpy(), pool_ref.pooled_outputs(arch, x.numpy(), [ei], ones),
+                               rtol=0, atol=1e-12)
+    masks = np.random.default_rng(6).random((3, x.shape[0])) < 0.5
+    masks[1] = True
+    (src, dst), = aggr_ref.kept_edges(masks, [ei])
+    batch = torch.arange(3).repeat_interleave(x.shape[0])
+    with torch.no_grad():
+        got = arch(x.repeat(3, 1), torch.as_tensor(np.stack([src, dst])), batch)
+    ref = pool_ref.pooled_outputs(arch, x.numpy(), [ei], masks)
+    assert tuple(got.shape) == (3, 2) and np.ptp(ref, axis=0).max() > 1e-4  # the masks matter
+    np.testing.assert_allclose(got.numpy(), ref, rtol=0, atol=1e-12)
+
+
+def test_global_pool_function():
+    h = torch.tensor([[1., -2.], [3., -4.], [-5., -6.]], dtype=torch.float64)
+    b = torch.tensor([0, 0, 2])
+    assert torch.equal(xnn.global_pool(h, b, "add"), torch.tensor([[4., -6.], [0., 0.], [-5., -6.]],
+                                                                 dtype=torch.float64))
+    assert torch.equal(xnn.global_pool(h, b, "mean")[0], torch.tensor([2., -3.], dtype=torch.float64))
+    assert torch.equal(xnn.global_pool(h, b, "max"), torch.tensor([[3., -2.], [0., 0.], [-5., -6.]],
+                                                                 dtype=torch.float64))
+    assert torch.equal(xnn.global_pool(h, None, "max"), torch.tensor([[3., -2.]], dtype=torch.float64))
+    assert tuple(xnn.global_pool(h, b, "sum", size=5).shape) == (5, 2)
+    with pytest.raises(ValueError, match="unknown pool"):
+        xnn.global_pool(h, b, "median")
+
+
+# ------------------------------------------------------------------ lowering
+@pytest.mark.parametrize("pool,want", [("mean", "mean"), ("add", "sum"), ("sum", "sum"), ("max", "max")])
+def test_compile_sets_pool_and_head(pool, want):
+    torch.manual_seed(1)
+    arch = pool_ref.model("gin", pool, dims=(6, 5, 4), fc=(4, 3, 2))
+    prog = compile_arch(arch)
+    assert prog.pool == want and prog.link_act is None
+    assert len(prog.head) == 2 and [h.act for h in prog.head] == ["relu", "sigmoid"]
+    assert torch.equal(prog.head[0].weight, arch.fc[0].weight.detach())
+    assert torch.equal(prog.head[1].bias, arch.fc[2].bias.detach())
+    enc = compile_arch(arch.encoder)
+    assert prog.hops == enc.hops == 2 and len(prog.convs) == len(enc.convs) == 4
+    assert enc.pool is None and not enc.head
+
+
+def test_compile_allows_hetero_single_type_and_gat_opt_in():
+    prog = compile_arch(pool_ref.model("hetero", "max"), edge_type_names=pool_ref.HETERO_RELS)
+    assert prog.pool == "max" and len(prog.convs[0].terms) == 3  # two mean terms + the summed root
+    gat = pool_ref.model("gat", "mean")
+    with pytest.raises(UnsupportedArch):
+        compile_arch(gat)
+    prog = compile_arch(gat, attention=True)
+    assert prog.pool == "mean" and prog.convs[0].terms[0].kind == "att"
+
+
+def test_existing_archs_have_no_pool():
+    assert compile_arch(xnn.ConvStack("gcn", [6, 5, 4], [4, 1])).pool is None
+    assert compile_arch(xnn.LinkModel(xnn.ConvStack("sage", [6, 5], [5, 4], final_act="identity"))).pool is None
+    assert compile_arch(xnn.RGCNStack([6, 5], [5, 1], 3)).pool is None
+
+
+def test_compile_refusals():
+    """Every refusal of the lowering: an encoder with a head, a link program, typed (rel) terms,
+    the multi-node-type lowering, an unknown pool."""
+    with pytest.raises(UnsupportedArch, match="Linear layers after its convs"):
+        compile_arch(xnn.PooledModel(xnn.ConvStack("gcn", [6, 5], [5, 4]), "mean", [4, 1]))
+    with pytest.raises(UnsupportedArch, match="link"):
+        compile_arch(xnn.PooledModel(xnn.LinkModel(xnn.ConvStack("gcn", [6, 5], [5])), "mean", [5, 1]))
+    with pytest.raises(UnsupportedArch, match="pooled encoder"):
+        compile_arch(xnn.LinkModel(pool_ref.model("gcn", "mean")))
+    with pytest.raises(UnsupportedArch, match="RGCNConv"):
+        compile_arch(xnn.PooledModel(xnn.RGCNStack([6, 5], [5], 3), "add", [5, 1]))
+    rels = [("a", "r", "b"), ("b", "s", "a")]
+    multi = xnn.PooledModel(xnn.HeteroSageStack(rels, {"a": 6, "b": 6}, 5, 1, [5]), "max", [5, 1])
+    with pytest.raises(UnsupportedArch, match="multi-node-type"):
+        compile_arch(multi, edge_type_names=rels, node_type_names=["a", "b"])
+    bad = pool_ref.model("gcn", "mean")
+    bad.pool = "median"
+    with pytest.raises(UnsupportedArch, match="pool='median'"):
+        compile_arch(bad)
+    with pytest.raises(ValueError, match="pool must be one of"):
+        xnn.PooledModel(xnn.ConvStack("gcn", [6, 5], [5]), "median", [5, 1])
+
+
+def test_infer_calls_the_three_parameter_form():
+    x, ei = _small(2)
+    torch.manual_seed(3)
+    arch = pool_ref.model("sage", "add", dims=(6, 5, 4), fc=(4, 1)).double()
+    eit = torch.as_tensor(ei)
+    batch = (torch.arange(x.shape[0]) >= 10).long()
+    out = Model(arch).infer(x, eit, batch=batch)
+    assert tuple(out.shape) == (2, 1)
+    with torch.no_grad():
+        assert torch.equal(out, arch(x, eit, batch))
+    assert tuple(Model(arch).infer(x, eit).shape) == (1, 1)  # batch=None: one graph
+    # the two existing conventions, and the error for anything else, are unchanged
+    two = xnn.ConvStack("gcn", [6, 4], [4, 1]).double()
+    assert tuple(Model(two).infer(x, eit).shape) == (x.shape[0], 1)
+    with pytest.raises(TypeError, match=r"\(x, edge_index, batch\)"):
+        Model(xnn.LinkModel(two)).infer(x, eit)
+
+
+# ------------------------------------------------------------------ descriptors (host only)
+def _pooled(layers, heads=(1,), pool=2, **kw):
+    desc = make_plan(layers, heads, **kw)
+    desc._keep[0][len(layers) - 1].pool = pool
+    return desc
+
+
+def _ws(desc, rows=70):
+    n = ctypes.c_size_t(0)
+    _lib.check(_lib.load().xpg_forward_workspace(ctypes.byref(desc), rows, ctypes.byref(n)))
+    return n.value
+
+
+def test_layer_desc_matches_header():
+    """`pool` is appended after seg_rel, the plan struct and the version are unchanged."""
+    assert [f[0] for f in _lib.LayerDesc._fields_][-2:] == ["seg_rel", "pool"]
+    assert _lib.ForwardPlanDesc._fields_[-1][0] == "dot_scale" and _lib.ABI_VERSION == 27
+    assert _lib.POOL == {None: 0, "mean": 1, "sum": 2, "max": 3}
+    assert {"xpg_pool_workspace", "xpg_pool_rows", "xpg_pool_describe"} <= set(_lib.EXPORTED)
+
+
+@pytest.mark.parametrize("layers,kw", [
+    ([(GCN, 32), (GCN, 32)], {"n_nodes": 40, "n_tgt": 40}),          # rows kernel without pool
+    ([(SAGE, 128), (SAGE, 128)], {"n_nodes": 10000, "n_tgt": 10000}),  # wide path without pool
+    ([(SAGE, 128), (SAGE, 128)], {}),
+])
+def test_pooled_plans_take_the_multi_kernel_path(layers, kw, monkeypatch):
+    plain = describe(make_plan(layers, **kw))
+    for pool in (1, 2, 3):
+        assert describe(_pooled(layers, pool=pool, **kw)) == "unfused"
+    assert plain in ("rows", "unfused") or plain.startswith("wide")
+    desc = _pooled(layers, **kw)
+    for forced in ("rows", "fused", "wide"):
+        monkeypatch.setenv("XPG_FORWARD", forced)
+        monkeypatch.delenv("XPG_FORWARD_STRICT", raising=False)
+        assert describe(desc) == "unfused"
+        monkeypatch.setenv("XPG_FORWARD_STRICT", "1")
+        with pytest.raises(RuntimeError, match="forced XPG_FORWARD path does not take this plan"):
+            describe(desc)
+        rc = _lib.load().xpg_masked_forward(ctypes.byref(desc), None, 70, None, None, 1 << 40, None)
+        assert rc == 1 and b"does not take this plan" in _lib.load().xpg_last_error()
+
+
+def _refused(desc, msg):
+    lib = _lib.load()
+    n = ctypes.c_size_t(0)
+    for rc in (lib.xpg_forward_workspace(ctypes.byref(desc), 70, ctypes.byref(n)),
+               lib.xpg_masked_forward(ctypes.byref(desc), None, 70, None, None, 1 << 40, None)):
+        assert rc == 1  # XPG_EINVAL: no pointer was read, nothing launched
+        assert msg in lib.xpg_last_error().decode()
+
+
+def test_host_checks():
+    layers = [(SAGE, 64), (SAGE, 64)]
+    d = make_plan(layers)
+    d._keep[0][0].pool = 2
+    _refused(d, "not the last conv layer")
+    d = _pooled(layers)
+    d.edge_masks = 1
+    _refused(d, "edge-mask plans (edge_masks)")
+    d = _pooled(layers)
+    d.edge_dot = 1
+    _refused(d, "link decoder (edge_dot)")
+    d = _pooled(layers)
+    d._keep[0][0].tgt_type = 256
+    _refused(d, "multi-node-type plans (tgt_type)")
+    for bad in (4, -1, 99):
+        _refused(_pooled(layers, pool=bad), "outside enum xpg_pool")
+
+
+def _part_nodes():
+    m = re.fullmatch(r"k_pool<sum> parts=1 part_nodes=(\d+)", _pool_describe(1, 1, 32, "sum"))
+    return int(m.group(1))
+
+
+def _pool_describe(rows, n, ld, kind):
+    buf = ctypes.create_string_buffer(128)
+    _lib.check(_lib.load().xpg_pool_describe(rows, n, ld, _lib.POOL[kind], buf, len(buf)))
+    return buf.value.decode()
+
+
+def _pool_ws(rows, n, ld):
+    nb = ctypes.c_size_t(0)
+    _lib.check(_lib.load().xpg_pool_workspace(rows, n, ld, ctypes.byref(nb)))
+    return nb.value
+
+
+@pytest.mark.parametrize("n_tgt", [1, 300, 513, 5000])
+@pytest.mark.parametrize("rows", [1, 70])
+def test_workspace_adds_exactly_the_documented_region(n_tgt, rows):
+    """Pooled = the same descriptor without pool + the pooled rows (rows * f_out_pad floats, to 256
+    bytes) + the partial rows (xpg_pool_workspace bytes, to 256 bytes)."""
+    up = lambda b: (b + 255) // 256 * 256
+    layers = [(SAGE, 64), (SAGE, 96)]
+    kw = {"n_nodes": max(n_tgt, 2), "n_tgt": n_tgt}
+    base = _ws(make_plan(layers, (8, 1), **kw), rows)
+    for pool in (1, 2, 3):
+        got = _ws(_pooled(layers, (8, 1), pool=pool, **kw), rows)
+        assert got == base + up(4 * rows * 96) + up(_pool_ws(rows, n_tgt, 96))
+    assert (_pool_ws(rows, n_tgt, 96) > 0) == (n_tgt > _part_nodes())
+
+
+def test_pool_describe_on_both_sides_of_the_split():
+    """One kernel up to part_nodes node rows (the launcher's own constant, read from its
+    description), two beyond; parts = ceil(n / part_nodes), whatever rows and ld."""
+    P = _part_nodes()
+    for kind in ("mean", "sum", "max"):
+        for rows, ld in ((1, 32), (70, 96), (3, 256)):
+            assert _pool_describe(rows, P, ld, kind) == f"k_pool<{kind}> parts=1 part_nodes={P}"
+            assert _pool_describe(rows, P + 1, ld, kind) == \
+                f"k_pool<{kind}>+k_pool_finish<{kind}> parts=2 part_nodes={P}"
+            assert _pool_describe(rows, 2 * P + 1, ld, kind).split()[1] == "parts=3"
+    assert _pool_ws(70, P, 96) == 0 and _pool_ws(70, P + 1, 96) == 4 * 70 * 2 * 96
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(128)
+    assert lib.xpg_pool_describe(1, 10, 32, 0, buf, 128) == 1   # XPG_POOL_NONE is no readout
+    assert lib.xpg_pool_describe(1, 10, 30, 2, buf, 128) == 1   # ld % 4
+    assert lib.xpg_pool_describe(1, 10, 260, 2, buf, 128) == 1  # ld > 256
+    assert lib.xpg_pool_describe(1, 0, 32, 2, buf, 128) == 1    # no node
+    assert lib.xpg_pool_describe(1, 10, 32, 2, buf, 4) == 3     # XPG_ENOSPC
+
+
+def test_stale_library_names_the_missing_symbol(monkeypatch, tmp_path):
+    """A library built before these exports: NativeLibraryError naming the symbol."""
+    class Old:
+        def __init__(self, real):
+            self._real = real
+
+        def __getattr__(self, name):
+            if name == "xpg_pool_rows":
+                raise AttributeError(name)
+            return getattr(self._real, name)
+    real = _lib.load()
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(ctypes, "CDLL", lambda path: Old(real))
+    with pytest.raises(_lib.NativeLibraryError, match="xpg_pool_rows"):
+        _lib.load()
+
+
+# ------------------------------------------------------------------ the GPU cases' sensitivity
+@pytest.mark.parametrize("feat", ["randn", "neg"])
+@pytest.mark.parametrize("pool", ["mean", "add", "max"])
+@pytest.mark.parametrize("kind", pool_ref.KINDS)
+def test_gpu_cases_are_sensitive(kind, pool, feat):
+    """On the reference alone, for the inputs tests/test_gpu_pool.py uses: at least half of the
+    sigmoid outputs off the tails, no conv pre-activation above 64, and at least half of the rows
+    more than 1e-3 (100 x the GPU bar) from the all-on row, so a wrong keep test cannot hide inside
+    the readout's averaging."""
+    c = pool_ref.hub_case(kind, pool, feat)
+    ref = c["ref"]
+    assert ref.shape == (70,) and c["masks"][1].all() and not c["masks"][0].any()
+    assert np.mean((ref > 0.02) & (ref < 0.98)) >= 0.5
+    assert c["pre"] <= 64
+    assert np.mean(np.abs(ref - ref[1]) > 1e-3) >= 0.5
