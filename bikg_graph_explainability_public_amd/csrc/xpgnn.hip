@@ -1292,6 +1292,236 @@ __global__ __launch_bounds__(256) void k_agg_att(AttArgs a) {
   }
 }
 
+// ------------------------------------------------------------------------------------ dynamic attention
+// XPG_TERM_ATT2 (GATv2Conv; the rules are in xpgnn.h).  The logit of an edge is
+// att_h . leaky_relu(XL[u] + XR[t]): the non-linearity sits between the sum and the dot product, so
+// no per-node score exists and every (mask row, kept edge, head) reduces head_ch products of
+// transformed rows.  The layer is transform-then-aggregate at every depth: sources are rows of XL
+// (layer 1: the plan's table, shared by the mask rows; deeper: k_dense's output for this call's
+// rows), the target's row of XR is held in registers.
+struct Att2Args {
+  int64_t rows;
+  int n_tgt, n_prev, n_terms;
+  int width;   // f_out_pad (floats, % 32 == 0, <= 256)
+  int chunks;  // width / 4: the lanes of an item that own a float4 of the row
+  int lanes;   // chunks rounded up to a power of two (8 / 16 / 32 / 64): an item sits inside one wave
+  const int32_t* tgt_prev;
+  const int32_t* tgt_f0;
+  const int32_t* agg_ptr;
+  const int32_t* agg_src;
+  const int32_t* agg_f0;
+  const int32_t* self_mult;
+  const int32_t* f0_node;
+  const uint32_t* bits;
+  int words;
+  int rel[XPG_MAX_TERMS];
+  int heads[XPG_MAX_TERMS];
+  int head_ch[XPG_MAX_TERMS];
+  int self_loops[XPG_MAX_TERMS];
+  float neg_slope[XPG_MAX_TERMS];
+  const float* xl[XPG_MAX_TERMS];   // row i of XL at xl + i * ld (layer 1: i = F_0 position;
+  const float* xr[XPG_MAX_TERMS];   // deeper: i = b * n_prev + position in the previous frontier)
+  const float* att[XPG_MAX_TERMS];  // [width], att[h][c] at h * head_ch + c, 0 past heads * head_ch
+  int ld[XPG_MAX_TERMS];
+  float* out;  // [rows][n_tgt][width]
+  const float* bias;
+  int act;
+  int f_real;
+};
+
+constexpr int kAtt2EB = 4;  // in-edges whose edge -> node -> keep word -> XL row loads are issued together
+
+// Sum over an aligned power-of-two subgroup of hl lanes (xor butterfly: quad DPP for 1 and 2, then
+// __shfl_xor); a + b == b + a exactly, so every lane of the subgroup ends with the same bits.
+__device__ __forceinline__ float att2_xor_sum(float x, int hl) {
+  if (hl > 1) x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xF, 0xF, false));  // quad_perm [1,0,3,2]
+  if (hl > 2) x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xF, 0xF, false));  // quad_perm [2,3,0,1]
+  for (int m = 4; m < hl; m <<= 1) x += __shfl_xor(x, m, 64);
+  return x;
+}
+
+// The logits of N source rows at the lane's columns.  ALIGNED (head_ch % 4 == 0, head_ch / 4 a
+// power of two): the lane's 4 columns share one head whose lanes are an aligned subgroup, z[q][0]
+// = that head's logit after one butterfly that serves every head at once.  Otherwise z[q][j] = the
+// logit of column j's head (0 for a column past heads * head_ch): heads inside one lane (head_ch 1
+// or 2) need no exchange; any other head_ch walks the heads, each a sum over the whole lane group
+// of the products that belong to it (chunks straddle heads there).
+template <bool ALIGNED, int N>
+__device__ __forceinline__ void att2_logits(const float4* v, const float4 xr, const float4 at, float slope, int H,
+                                            int C, int lanes, int f0, float (*z)[ALIGNED ? 1 : 4]) {
+  float p[N][4];
+#pragma unroll
+  for (int q = 0; q < N; ++q) {
+    p[q][0] = at.x * leaky(v[q].x + xr.x, slope);
+    p[q][1] = at.y * leaky(v[q].y + xr.y, slope);
+    p[q][2] = at.z * leaky(v[q].z + xr.z, slope);
+    p[q][3] = at.w * leaky(v[q].w + xr.w, slope);
+  }
+  if constexpr (ALIGNED) {
+    const int hl = C >> 2;
+#pragma unroll
+    for (int q = 0; q < N; ++q) z[q][0] = att2_xor_sum((p[q][0] + p[q][1]) + (p[q][2] + p[q][3]), hl);
+  } else {
+    if (C == 1) {
+#pragma unroll
+      for (int q = 0; q < N; ++q)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) z[q][j] = p[q][j];
+    } else if (C == 2) {
+#pragma unroll
+      for (int q = 0; q < N; ++q) {
+        z[q][0] = z[q][1] = p[q][0] + p[q][1];
+        z[q][2] = z[q][3] = p[q][2] + p[q][3];
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < N; ++q)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) z[q][j] = 0.f;
+      for (int h = 0; h < H; ++h) {
+        const int c0 = h * C - f0;  // the head's columns, relative to the lane's first: [c0, c0 + C)
+        bool in[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) in[j] = j >= c0 && j < c0 + C;
+        float s[N];
+#pragma unroll
+        for (int q = 0; q < N; ++q)
+          s[q] = ((in[0] ? p[q][0] : 0.f) + (in[1] ? p[q][1] : 0.f)) + ((in[2] ? p[q][2] : 0.f) + (in[3] ? p[q][3] : 0.f));
+        for (int m = 1; m < lanes; m <<= 1) {
+#pragma unroll
+          for (int q = 0; q < N; ++q) s[q] += __shfl_xor(s[q], m, 64);
+        }
+#pragma unroll
+        for (int q = 0; q < N; ++q)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) z[q][j] = in[j] ? s[q] : z[q][j];
+      }
+    }
+  }
+}
+
+// One online-softmax step over N entries (kp: which take part; mult: the multiplicity of each, the
+// self-loop copies): running max m with a rescale of the denominator and the accumulator, so every
+// source row is read once.  The caller skips the step when no entry takes part, so the new max is
+// finite and a first step computes exp(-inf - finite) = 0, never (-inf) - (-inf).
+template <bool ALIGNED, int N>
+__device__ __forceinline__ void att2_step(const float4* v, const bool* kp, float mult, float (*z)[ALIGNED ? 1 : 4],
+                                          float* m, float* den, float* acc) {
+  constexpr int NS = ALIGNED ? 1 : 4;
+  float sc[NS], pw[N][NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    float mn = m[s];
+#pragma unroll
+    for (int q = 0; q < N; ++q) mn = kp[q] ? fmaxf(mn, z[q][s]) : mn;
+    sc[s] = __expf(m[s] - mn);
+    m[s] = mn;
+    float d = den[s] * sc[s];
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+      pw[q][s] = kp[q] ? __expf(z[q][s] - mn) * mult : 0.f;
+      d += pw[q][s];
+    }
+    den[s] = d;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) acc[j] *= sc[ALIGNED ? 0 : j];
+#pragma unroll
+  for (int q = 0; q < N; ++q) {
+    acc[0] = fmaf(pw[q][0], v[q].x, acc[0]);
+    acc[1] = fmaf(pw[q][ALIGNED ? 0 : 1], v[q].y, acc[1]);
+    acc[2] = fmaf(pw[q][ALIGNED ? 0 : 2], v[q].z, acc[2]);
+    acc[3] = fmaf(pw[q][ALIGNED ? 0 : 3], v[q].w, acc[3]);
+  }
+}
+
+// A guarded float4 load as a value (a conditional between two lvalues would select between
+// addresses and put the zero operand in scratch).
+__device__ __forceinline__ float4 att2_ld4(bool on, const float* p) {
+  float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (on) r = *reinterpret_cast<const float4*>(p);
+  return r;
+}
+
+// Dynamic-attention aggregation of one conv layer, the whole layer in one launch.  Item = (mask
+// row b, target t) on `lanes` lanes of one wave, lane `sub` owns float4 chunk `sub` of the row
+// (lanes past `chunks` load nothing and add zeros to the exchanges).  Every branch and loop bound
+// below is the same for all lanes of an item, so the lanes that exchange data are active together.
+// The result for (b, t) depends on the plan and mask row b alone; the epilogue is k_agg_att<true>'s.
+template <bool L1, bool ALIGNED>
+__global__ __launch_bounds__(256) void k_agg_att2(Att2Args a) {
+  constexpr int EB = kAtt2EB;
+  constexpr int NS = ALIGNED ? 1 : 4;
+  const int64_t item = blockIdx.x * (int64_t)(256 / a.lanes) + threadIdx.x / a.lanes;
+  const int sub = threadIdx.x & (a.lanes - 1);
+  if (item >= a.rows * a.n_tgt) return;
+  const int64_t b = item / a.n_tgt;
+  const int t = static_cast<int>(item - b * a.n_tgt);
+  const uint32_t* mrow = a.bits + b * a.words;
+  const int t0 = a.tgt_f0[t];
+  const int tp = a.tgt_prev[t];
+  const bool t_on = bit_of(mrow, a.f0_node[t0]);
+  const bool live = sub < a.chunks;
+  const int f0 = sub * 4;
+  float tot[4] = {0.f, 0.f, 0.f, 0.f};
+
+  for (int k = 0; k < a.n_terms; ++k) {
+    const int H = a.heads[k], C = a.head_ch[k], r = a.rel[k];
+    const float slope = a.neg_slope[k];
+    const int* pp = a.agg_ptr + (int64_t)r * (a.n_tgt + 1);
+    // non-self in-edges take part only while the target itself is kept
+    const int e0 = pp[t], e1 = t_on ? pp[t + 1] : pp[t];
+    const int n_self = a.self_loops[k] ? 1 : (t_on ? a.self_mult[(int64_t)r * a.n_tgt + t] : 0);
+    const int64_t ld = a.ld[k];
+    const int64_t row0 = L1 ? 0 : b * (int64_t)a.n_prev;
+    const int self_pos = L1 ? t0 : tp;
+    const float* xl = a.xl[k] + row0 * ld + f0;
+    const float4 xr = att2_ld4(live, a.xr[k] + (row0 + self_pos) * ld + f0);
+    const float4 at = att2_ld4(live, a.att[k] + f0);
+    float m[NS], den[NS], acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      m[s] = -INFINITY;
+      den[s] = 0.f;
+    }
+    if (n_self > 0) {  // the loop's source row is XL[t]
+      const float4 v = att2_ld4(live, xl + self_pos * ld);
+      const bool kp = true;
+      float z[1][NS];
+      att2_logits<ALIGNED, 1>(&v, xr, at, slope, H, C, a.lanes, f0, z);
+      att2_step<ALIGNED, 1>(&v, &kp, static_cast<float>(n_self), z, m, den, acc);
+    }
+    for (int eb = e0; eb < e1; eb += EB) {
+      int up[EB], nd[EB];
+      bool kp[EB];
+      float4 v[EB];
+#pragma unroll
+      for (int q = 0; q < EB; ++q) {
+        const int e = eb + q < e1 ? eb + q : eb;
+        nd[q] = a.agg_f0[e];
+        up[q] = L1 ? nd[q] : a.agg_src[e];
+      }
+#pragma unroll
+      for (int q = 0; q < EB; ++q) nd[q] = a.f0_node[nd[q]];
+#pragma unroll
+      for (int q = 0; q < EB; ++q) kp[q] = bit_of(mrow, nd[q]) && eb + q < e1;
+#pragma unroll
+      for (int q = 0; q < EB; ++q) v[q] = att2_ld4(kp[q] && live, xl + up[q] * ld);
+      if (!(kp[0] || kp[1] || kp[2] || kp[3])) continue;
+      float z[EB][NS];
+      att2_logits<ALIGNED, EB>(v, xr, at, slope, H, C, a.lanes, f0, z);
+      att2_step<ALIGNED, EB>(v, kp, 1.f, z, m, den, acc);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) tot[j] += acc[j] * (1.f / (den[ALIGNED ? 0 : j] + 1e-16f));
+  }
+  if (!live) return;
+  float o[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) o[q] = (f0 + q < a.f_real) ? act_apply(tot[q] + a.bias[f0 + q], a.act) : 0.f;
+  reinterpret_cast<float4*>(a.out + item * a.width)[sub] = make_float4(o[0], o[1], o[2], o[3]);
+}
+
 // ------------------------------------------------------------------------------------ typed relations
 // XPG_TERM_REL (RGCNConv / FastRGCNConv; the rules are in xpgnn.h): one term for every relation of
 // the plan.  A kernel of its own: k_agg walks its terms with one pointer pair per (term, target),
@@ -6187,10 +6417,47 @@ bool layer_has_attention(const xpg_layer_desc& ly) {
     if (ly.terms[k].kind == XPG_TERM_ATT) return true;
   return false;
 }
+// dynamic attention (XPG_TERM_ATT2, the v27 addendum): layers of their own on the same path
+bool layer_has_att2(const xpg_layer_desc& ly) {
+  for (int k = 0; k < ly.n_terms && k < XPG_MAX_TERMS; ++k)
+    if (ly.terms[k].kind == XPG_TERM_ATT2) return true;
+  return false;
+}
 bool plan_has_attention(const xpg_forward_plan* p) {
   for (int l = 0; l < p->n_layers; ++l)
-    if (layer_has_attention(p->layers[l])) return true;
+    if (layer_has_attention(p->layers[l]) || layer_has_att2(p->layers[l])) return true;
   return false;
+}
+// The argument rules of ATT2 layers (xpgnn.h), checked on the host before anything is launched and
+// without reading through any of the plan's device pointers.
+int att2_plan_check(const xpg_forward_plan* p) {
+  for (int l = 0; l < p->n_layers; ++l) {
+    const xpg_layer_desc& ly = p->layers[l];
+    if (!layer_has_att2(ly)) continue;
+    XPG_REQ(ly.n_terms >= 1 && ly.n_terms <= XPG_MAX_TERMS, "layer: 1..8 terms");
+    XPG_REQ(!p->edge_masks, "ATT2 terms do not take edge-mask plans (edge_masks)");
+    XPG_REQ(!ly.tgt_type, "ATT2 layer: multi-node-type plans (tgt_type) are not taken");
+    XPG_REQ(p->f0_node, "ATT2 terms need f0_node");
+    XPG_REQ(ly.f_out_pad > 0 && ly.f_out_pad % 32 == 0 && ly.f_out_pad <= 256,
+            "ATT2 layer: f_out_pad must be 32..256, a multiple of 32");
+    XPG_REQ(l > 0 || !(ly.weight && ly.f_in_pad > 0), "ATT2 layer 1 does not take the raw form");
+    XPG_REQ(!ly.weight, "ATT2 layer: weight must be NULL (the terms carry W_l / W_r)");
+    XPG_REQ(l == 0 || (ly.f_in_pad == p->layers[l - 1].f_out_pad && ly.f_in_pad % 8 == 0),
+            "layer: f_in_pad must equal previous f_out_pad");
+    XPG_REQ(ly.bias, "ATT2 layer: bias missing");
+    for (int k = 0; k < ly.n_terms; ++k) {
+      const xpg_term_desc& td = ly.terms[k];
+      XPG_REQ(td.kind == XPG_TERM_ATT2, "layer: ATT2 terms cannot be mixed with other kinds");
+      XPG_REQ(td.rel >= 0 && td.rel < p->n_rel, "term: bad relation");
+      XPG_REQ(td.dst_type == -1, "ATT2 term: dst_type must be -1");
+      XPG_REQ(td.heads >= 1 && td.head_ch >= 1 && (int64_t)td.heads * td.head_ch <= ly.f_out_pad,
+              "ATT2 term: heads * head_ch must fit the layer's output width");
+      XPG_REQ(td.att_src && td.table, "ATT2 term: missing att_src or table");
+      XPG_REQ(l > 0 || td.att_dst, "ATT2 term: layer 1 needs att_dst (the XR table)");
+      XPG_REQ(l == 0 || td.coef, "ATT2 term: a deeper layer needs coef (the biases b_l, b_r)");
+    }
+  }
+  return XPG_OK;
 }
 // typed-relation (XPG_TERM_REL, v26) layers run on the multi-kernel path only
 bool layer_has_rel(const xpg_layer_desc& ly) {
@@ -6209,7 +6476,7 @@ bool plan_needs_degree(const xpg_forward_plan* p) {
   if (plan_has_rel(p)) return false;  // edge masks included: the EM kernels test the edge columns
   for (int l = 0; l < p->n_layers; ++l)
     for (int k = 0; k < p->layers[l].n_terms && k < XPG_MAX_TERMS; ++k)
-      if (p->layers[l].terms[k].kind != XPG_TERM_ATT) return true;
+      if (p->layers[l].terms[k].kind != XPG_TERM_ATT && p->layers[l].terms[k].kind != XPG_TERM_ATT2) return true;
   return p->edge_masks != 0;
 }
 // SUM / MAX terms (v25) and the raw (aggregate-then-transform) layer 1 that MAX needs there: the
@@ -6253,7 +6520,7 @@ int deg_pitch(const xpg_forward_plan* p) {
 }
 
 struct WsLayout {
-  size_t kin = 0, agg = 0, head0 = 0, head1 = 0, score = 0, ctl = 0, total = 0;
+  size_t kin = 0, agg = 0, head0 = 0, head1 = 0, score = 0, xlr = 0, ctl = 0, total = 0;
   size_t h[64];
   size_t pool = 0, pool_part = 0, pool_part_bytes = 0;  // pooled plans only: the region after ctl
 };
@@ -6261,14 +6528,22 @@ struct WsLayout {
 int layout_ws(const xpg_forward_plan* p, int64_t rows, WsLayout* L) {
   XPG_REQ(p && p->n_layers >= 1 && p->n_layers <= 64, "plan: 1..64 conv layers required");
   if (const int rc = pool_plan_check(p)) return rc;
+  if (const int rc = att2_plan_check(p)) return rc;
   size_t off = 0;
   L->kin = off;  // REL plans read no degrees: no region (n_rel can be in the hundreds)
   if (!plan_has_rel(p)) off += align_up(sizeof(float) * (size_t)rows * p->n_rel * deg_pitch(p));
-  size_t agg_max = 0, score_max = 0;
+  size_t agg_max = 0, score_max = 0, xlr_max = 0;
   for (int l = 0; l < p->n_layers; ++l) {
     const xpg_layer_desc& ly = p->layers[l];
     L->h[l] = off;
     off += align_up(sizeof(float) * (size_t)rows * ly.n_tgt * ly.f_out_pad);
+    if (layer_has_att2(ly)) {  // transform-then-aggregate: no dense input, no scores
+      if (l > 0) {             // XL | XR of every previous-frontier row, per term
+        size_t x = sizeof(float) * (size_t)rows * p->layers[l - 1].n_tgt * 2 * ly.n_terms * ly.f_out_pad;
+        xlr_max = x > xlr_max ? x : xlr_max;
+      }
+      continue;
+    }
     if (l > 0 || plan_raw_l1(p)) {  // the layer's dense input (layer 1: its raw form only)
       size_t a = sizeof(float) * (size_t)rows * ly.n_tgt * layer_slices(ly) * ly.f_in_pad;
       agg_max = a > agg_max ? a : agg_max;
@@ -6292,6 +6567,8 @@ int layout_ws(const xpg_forward_plan* p, int64_t rows, WsLayout* L) {
   off += align_up(hmax);
   L->score = off;  // attention layers' score pre-pass (0 bytes for plans without ATT terms)
   off += align_up(score_max);
+  L->xlr = off;  // ATT2 layers past the first: the transformed rows (0 bytes for plans without them)
+  off += align_up(xlr_max);
   L->ctl = off;  // the rows forward's block-scheduling counters (zeroed before each launch)
   off += align_up(sizeof(int) * 32);
   if (plan_pool(p)) {  // the pooled rows, then the partial rows of a split readout
@@ -6460,6 +6737,87 @@ int launch_att_layer(const xpg_forward_plan* p, int l, const uint32_t* bits, int
   hipLaunchKernelGGL(k_att_score, dim3(static_cast<unsigned>(cdiv(n_sc, 256))), block, 0, st, a);
   XPG_LAUNCHED();
   hipLaunchKernelGGL(k_agg_att<false>, grid, block, 0, st, a);
+  XPG_LAUNCHED();
+  return XPG_OK;
+}
+
+// One dynamic-attention layer (every term XPG_TERM_ATT2, att2_plan_check passed), finished into
+// hout: layer 1 is one k_agg_att2<true> launch on the plan's XL / XR tables; a deeper layer first
+// transforms every previous-frontier row of this call (k_dense, bias from coef, no activation)
+// into the xlr region, per term one [rows * n_prev][2 * f_out_pad] block holding XL | XR (one
+// launch when both fit k_dense's 256 columns, else two; shared weights, n_slices == 1: one
+// [f_out_pad]-wide block read for both), then aggregates.  No dense launch follows.
+int launch_att2_layer(const xpg_forward_plan* p, int l, const uint32_t* bits, int64_t rows, const float* hprev,
+                      float* xlr, float* out, hipStream_t st) {
+  const xpg_layer_desc& ly = p->layers[l];
+  Att2Args a;
+  std::memset(&a, 0, sizeof(a));
+  a.rows = rows;
+  a.n_tgt = ly.n_tgt;
+  a.n_prev = l == 0 ? p->n0 : p->layers[l - 1].n_tgt;
+  a.n_terms = ly.n_terms;
+  a.width = ly.f_out_pad;
+  a.chunks = a.width / 4;
+  a.lanes = a.chunks <= 8 ? 8 : a.chunks <= 16 ? 16 : a.chunks <= 32 ? 32 : 64;
+  a.tgt_prev = ly.tgt_prev;
+  a.tgt_f0 = ly.tgt_f0;
+  a.agg_ptr = ly.agg_ptr;
+  a.agg_src = ly.agg_src;
+  a.agg_f0 = ly.agg_f0;
+  a.self_mult = ly.self_mult;
+  a.f0_node = p->f0_node;
+  a.bits = bits;
+  a.words = words_of(p->cols);
+  a.out = out;
+  a.bias = ly.bias;
+  a.act = ly.act;
+  a.f_real = ly.f_out;
+  bool aligned = true;
+  const int64_t n_in = rows * a.n_prev;  // rows of the layer's input
+  float* blk = xlr;
+  for (int k = 0; k < ly.n_terms; ++k) {
+    const xpg_term_desc& td = ly.terms[k];
+    const int hl = td.head_ch / 4;
+    aligned = aligned && td.head_ch % 4 == 0 && (hl & (hl - 1)) == 0;
+    a.rel[k] = td.rel;
+    a.heads[k] = td.heads;
+    a.head_ch[k] = td.head_ch;
+    a.self_loops[k] = td.self_loops ? 1 : 0;
+    a.neg_slope[k] = td.neg_slope;
+    a.att[k] = td.att_src;
+    if (l == 0) {
+      a.xl[k] = td.table;
+      a.xr[k] = td.att_dst;
+      a.ld[k] = ly.f_out_pad;
+      continue;
+    }
+    const bool shared = td.n_slices == 1;
+    const int64_t np = ly.f_out_pad, ldc = shared ? np : 2 * np;
+    if (shared || 2 * np <= 256) {
+      if (const int rc = launch_dense(hprev, n_in, ly.f_in_pad, td.table, ly.f_in_pad, ly.f_in_pad, td.coef, ldc, ldc,
+                                      XPG_ACT_NONE, blk, ldc, st))
+        return rc;
+    } else {
+      for (int s = 0; s < 2; ++s)
+        if (const int rc = launch_dense(hprev, n_in, ly.f_in_pad, td.table + s * np * ly.f_in_pad, ly.f_in_pad,
+                                        ly.f_in_pad, td.coef + s * np, np, np, XPG_ACT_NONE, blk + s * np, ldc, st))
+          return rc;
+    }
+    a.xl[k] = blk;
+    a.xr[k] = shared ? blk : blk + np;
+    a.ld[k] = static_cast<int>(ldc);
+    blk += n_in * 2 * np;
+  }
+  const int64_t items = rows * ly.n_tgt;
+  if (items == 0) return XPG_OK;
+  const dim3 grid(static_cast<unsigned>(cdiv(items, 256 / a.lanes))), block(256);
+  if (l == 0) {
+    if (aligned) hipLaunchKernelGGL((k_agg_att2<true, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_agg_att2<true, false>), grid, block, 0, st, a);
+  } else {
+    if (aligned) hipLaunchKernelGGL((k_agg_att2<false, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_agg_att2<false, false>), grid, block, 0, st, a);
+  }
   XPG_LAUNCHED();
   return XPG_OK;
 }
@@ -7870,8 +8228,10 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
   bool fuse_out = false;
   // A pooled plan's head follows the readout, which is no dense layer: its last head layer is
   // fused only into the head layer before it (k_dense HEAD on M = rows rows, as for one query).
+  // Nor does an ATT2 last layer end in a dense launch (k_agg_att2 finishes the layer itself).
   const int pool = plan_pool(p);
-  if (!p->edge_dot && p->n_head >= 1 && (p->n_head >= 2 || (p->n_layers >= 2 && !pool))) {
+  const bool last_att2 = layer_has_att2(p->layers[p->n_layers - 1]);
+  if (!p->edge_dot && p->n_head >= 1 && (p->n_head >= 2 || (p->n_layers >= 2 && !pool && !last_att2))) {
     const xpg_head_desc& hl = p->head[p->n_head - 1];
     const int64_t prev_pad = p->n_head >= 2 ? p->head[p->n_head - 2].n_pad : p->layers[p->n_layers - 1].f_out_pad;
     if (hl.k_pad == prev_pad && p->out_col >= 0 && p->out_col < hl.n_real) {
@@ -7893,6 +8253,12 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
     const xpg_layer_desc& ly = p->layers[l];
     XPG_REQ(ly.n_terms >= 1 && ly.n_terms <= XPG_MAX_TERMS, "layer: 1..8 terms");
     const bool raw = l == 0 && plan_raw_l1(p);
+    if (layer_has_att2(ly)) {
+      rc = launch_att2_layer(p, l, bits, rows, l == 0 ? nullptr : reinterpret_cast<const float*>(ws + L.h[l - 1]),
+                             reinterpret_cast<float*>(ws + L.xlr), reinterpret_cast<float*>(ws + L.h[l]), st);
+      if (rc) return rc;
+      continue;
+    }
     if (layer_has_attention(ly)) {
       XPG_REQ(!raw, "layer 1: attention terms do not take the raw form");
       float* hout = reinterpret_cast<float*>(ws + L.h[l]);

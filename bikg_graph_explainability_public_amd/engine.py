@@ -741,6 +741,24 @@ def _rel_tables(X0, W, f_out_pad, device):
         T[r0:r0 + n] = C.reshape(n0, n, f_out_pad).permute(1, 0, 2)
     return T
 
+
+def _dev(t, device):
+    return None if t is None else t.to(device)
+
+
+def _pad_vec(v, n, device):
+    out = torch.zeros(n, dtype=torch.float32, device=device)
+    out[:v.numel()] = v.to(device=device, dtype=torch.float32)
+    return out
+
+
+def _pad_table(T, n):
+    """[rows, n] fp32 copy of T with zero columns past its own."""
+    out = torch.zeros((T.shape[0], n), dtype=torch.float32, device=T.device)
+    out[:, :T.shape[1]] = T
+    return out
+
+
 # ForwardPlan drops the relation terms of other destination types from a layer whose targets
 # share one node type (they add exactly 0); False keeps every term (the parity suite's reference)
 PLAN_DROP_OTHER_TYPES = True
@@ -845,6 +863,12 @@ class ForwardPlan:
                 raise ValueError("a conv layer mixing attention with other terms is not supported")
             if att and self.edge_masks:
                 raise ValueError("attention terms on edge-mask plans are not supported")
+            att2 = any(t.kind == "att2" for t in terms)
+            if att2 and not all(t.kind == "att2" for t in terms):
+                raise ValueError("a conv layer mixing dynamic attention with other terms is not supported")
+            if att2 and (self.edge_masks or program.n_types > 1):
+                raise ValueError("dynamic-attention terms on edge-mask or multi-node-type plans "
+                                 "are not supported")
             if self.edge_masks and any(t.kind in ("sum", "max") for t in terms):
                 raise ValueError("sum / max terms on edge-mask plans are not supported")
             rel = [t for t in terms if t.kind == "rel"]
@@ -933,6 +957,16 @@ class ForwardPlan:
                     ld.terms[k].heads, ld.terms[k].head_ch = term.heads, term.head_ch
                     ld.terms[k].neg_slope = term.neg_slope
                     ld.terms[k].self_loops = int(term.self_loops)
+                if term.kind == "att2":
+                    ld.terms[k].heads, ld.terms[k].head_ch = term.heads, term.head_ch
+                    ld.terms[k].neg_slope = term.neg_slope
+                    ld.terms[k].self_loops = int(term.self_loops)
+                    ld.terms[k].dst_type = -1
+                    att_p = self._program_tensor(
+                        program, ("att2_att", li, id(term)),
+                        lambda term=term, f_out_pad=f_out_pad: _pad_vec(term.att.reshape(-1), f_out_pad, device))
+                    self._keep.append(att_p)
+                    ld.terms[k].att_src = att_p.data_ptr()
                 if term.kind == "rel":
                     ld.terms[k].n_slices = self.n_rel if li == 0 else term.slices
                     ld.terms[k].norm = REL_NORM[term.norm]
@@ -953,6 +987,17 @@ class ForwardPlan:
                         self._keep.append(Tp)
                         ld.terms[k].table = Tp.data_ptr()
                         continue
+                    if term.kind == "att2":
+                        # XL / XR of the F_0 nodes, shared by every mask row (features are never
+                        # masked): X0 W_l^T + b_l and X0 W_r^T + b_r, padded columns 0
+                        XL = _pad_table(dense(X0, term.weight.to(device), _dev(term.bias_l, device)),
+                                        f_out_pad)
+                        XR = XL if term.weight_r is None else \
+                            _pad_table(dense(X0, term.weight_r.to(device), _dev(term.bias_r, device)),
+                                       f_out_pad)
+                        self._keep += [XL, XR]
+                        ld.terms[k].table, ld.terms[k].att_dst = XL.data_ptr(), XR.data_ptr()
+                        continue
                     T = dense(X0, term.weight.to(device), None, None)
                     Tp = torch.zeros((n0, f_out_pad), dtype=torch.float32, device=device)
                     Tp[:, :conv.f_out] = T
@@ -970,6 +1015,25 @@ class ForwardPlan:
                         self._keep += [a_s, a_d]
                         ld.terms[k].att_src, ld.terms[k].att_dst = a_s.data_ptr(), a_d.data_ptr()
                 ld.weight = None
+            elif att2:
+                # transform-then-aggregate: per term the stacked [W_l; W_r] (one block when
+                # shared) and [b_l; b_r], zero-padded; the layer itself has no weight
+                ld.weight = None
+                for k, term in enumerate(terms):
+                    def make_att2(term=term, prev_pad=prev_pad, f_out_pad=f_out_pad):
+                        ws = [term.weight] + ([] if term.weight_r is None else [term.weight_r])
+                        bs = [term.bias_l] + ([] if term.weight_r is None else [term.bias_r])
+                        w = torch.zeros((len(ws), f_out_pad, prev_pad), dtype=torch.float32, device=device)
+                        b = torch.zeros((len(ws), f_out_pad), dtype=torch.float32, device=device)
+                        for i, (wi, bi) in enumerate(zip(ws, bs)):
+                            w[i, :wi.shape[0], :wi.shape[1]] = wi.to(device)
+                            if bi is not None:
+                                b[i, :bi.shape[0]] = bi.to(device)
+                        return w, b
+                    w2, b2 = self._program_tensor(program, ("att2_w", li, id(term)), make_att2)
+                    self._keep += [w2, b2]
+                    ld.terms[k].table, ld.terms[k].coef = w2.data_ptr(), b2.data_ptr()
+                    ld.terms[k].n_slices = w2.shape[0]  # 1: shared weights
             elif att:
                 # one f_in_pad-wide slice of the dense input per (term, head): head h's rows of
                 # W_src in slice (k, h), zeros elsewhere, so the layer stays aggregate-then-transform

@@ -277,6 +277,66 @@ class GATConv(MessagePassing):
         return f"{self.in_channels}, {self.out_channels}, heads={self.heads}"
 
 
+class GATv2Conv(MessagePassing):
+    """GATv2Conv (PyG 2.0.4), "dynamic" attention: x_l = lin_l(x), x_r = lin_r(x) (lin_r is lin_l
+    with share_weights), logit of edge (u -> t), head h: att[h] . leaky_relu(x_l[u, h] + x_r[t, h],
+    negative_slope), softmax over each target's in-edges, out[t, h] = sum alpha x_l[u, h] (the
+    lin_l bias travels inside the messages), heads concatenated (or averaged), + bias.  State-dict
+    keys lin_l.weight / lin_l.bias / lin_r.weight / lin_r.bias / att / bias.  Archs using it run on
+    the generic torch path unless the attention opt-in is set (Explainer
+    params["attention_engine"] = True, program.compile_arch(..., attention=True)): then the engine
+    compiles it to its dynamic-attention HIP kernel (concat=True, or concat=False with one head; no
+    edge_dim; Tensor input, int in_channels)."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2,
+                 dropout=0.0, add_self_loops=True, bias=True, share_weights=False, **kwargs):
+        super().__init__()
+        if not isinstance(in_channels, int):
+            raise NotImplementedError("GATv2Conv takes an int in_channels (Tensor input)")
+        self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
+        self.concat, self.negative_slope, self.dropout = concat, negative_slope, dropout
+        self.add_self_loops, self.share_weights = add_self_loops, share_weights
+        self.lin_l = Linear(in_channels, heads * out_channels, bias=bias, weight_initializer="glorot",
+                            bias_initializer="zeros")
+        self.lin_r = self.lin_l if share_weights else \
+            Linear(in_channels, heads * out_channels, bias=bias, weight_initializer="glorot",
+                   bias_initializer="zeros")
+        self.att = nn.Parameter(torch.empty(1, heads, out_channels))
+        _uniform_(self.att, math.sqrt(6.0 / (heads + out_channels)))
+        n_bias = heads * out_channels if concat else out_channels
+        self.bias = nn.Parameter(torch.zeros(n_bias)) if bias else None
+
+    def forward(self, x, edge_index):
+        H, C = self.heads, self.out_channels
+        xl = self.lin_l(x).view(-1, H, C)
+        xr = xl if self.share_weights else self.lin_r(x).view(-1, H, C)
+        ei = edge_index.long()
+        n = xl.size(0)
+        if self.add_self_loops:
+            loop = torch.arange(n, device=ei.device)
+            ei = torch.cat([ei[:, ei[0] != ei[1]], torch.stack([loop, loop])], 1)
+        src, dst = ei[0], ei[1]
+        e = F.leaky_relu(xl[src] + xr[dst], self.negative_slope)
+        alpha = (e * self.att).sum(-1)                                           # [E, H]
+        idx = dst.unsqueeze(1).expand(-1, H)
+        amax = torch.zeros((n, H), dtype=alpha.dtype, device=alpha.device).scatter_reduce(
+            0, idx, alpha, reduce="amax", include_self=False)
+        ex = (alpha - amax[dst]).exp()
+        den = torch.zeros((n, H), dtype=alpha.dtype, device=alpha.device).index_add_(0, dst, ex)
+        alpha = ex / (den[dst] + 1e-16)
+        alpha = F.dropout(alpha, p=self.dropout, training=self.training)
+        out = torch.zeros((n, H, C), dtype=xl.dtype, device=xl.device)
+        out.index_add_(0, dst, xl[src] * alpha.unsqueeze(-1))
+        out = out.reshape(n, H * C) if self.concat else out.mean(dim=1)
+        if self.bias is not None:
+            out = out + self.bias
+        return out
+
+    def extra_repr(self):
+        return (f"{self.in_channels}, {self.out_channels}, heads={self.heads}, "
+                f"share_weights={self.share_weights}")
+
+
 class RGCNConv(MessagePassing):
     """RGCNConv (PyG 2.0.4, dense features): out[t] = sum_r AGG_{e = (u -> t), type(e) = r} x_u W_r
     + x_t root + bias, W_r [in, out] (not Linear's [out, in]).  `aggr` = mean (the default; per
@@ -391,23 +451,31 @@ class ConvStack(nn.Module):
     (GINConv over Sequential(Linear, ReLU, Linear)); `hetero_rels`
     wraps each conv in HeteroConv over the given edge types (single node type).  "gat":
     GATConv layers with `heads[i]` concatenated heads of dims[i + 1] channels (default all 1), so
-    layer i reads dims[i] * heads[i - 1] columns and the head reads dims[-1] * heads[-1]."""
+    layer i reads dims[i] * heads[i - 1] columns and the head reads dims[-1] * heads[-1].
+    "gatv2": the same with GATv2Conv layers; `share_weights` is handed to them."""
 
     def __init__(self, kind, dims, fc_dims, hetero_rels=None, final_act="sigmoid", heads=None,
-                 add_self_loops=True):
+                 add_self_loops=True, share_weights=False):
         super().__init__()
         n_conv = len(dims) - 1
-        if kind == "gat":
+        if kind in ("gat", "gatv2"):
             heads = [1] * n_conv if heads is None else [int(h) for h in heads]
             if len(heads) != n_conv:
                 raise ValueError("heads must give one entry per conv layer")
+            if share_weights and kind != "gatv2":
+                raise ValueError("share_weights applies to kind='gatv2' only")
 
             def mk(f_in, f_out, i):
-                return GATConv(f_in * (heads[i - 1] if i else 1), f_out, heads=heads[i],
-                               add_self_loops=add_self_loops)
+                f_in = f_in * (heads[i - 1] if i else 1)
+                if kind == "gatv2":
+                    return GATv2Conv(f_in, f_out, heads=heads[i], add_self_loops=add_self_loops,
+                                     share_weights=share_weights)
+                return GATConv(f_in, f_out, heads=heads[i], add_self_loops=add_self_loops)
         else:
             if heads is not None:
-                raise ValueError("heads applies to kind='gat' only")
+                raise ValueError("heads applies to kind='gat' / 'gatv2' only")
+            if share_weights:
+                raise ValueError("share_weights applies to kind='gatv2' only")
             makers = {
                 "gcn": GCNConv, "sage": SAGEConv,
                 "sage-add": lambda i, o: SAGEConv(i, o, aggr="add"),

@@ -3,7 +3,7 @@
 The reference treats `arch` as a black box and calls `arch(feat, edge_index)` on the B-fold
 union graph (model.py:62-116).  The engine instead recognises the supported module family —
 GCNConv / SAGEConv (mean, add, max) / GraphConv / GINConv / HeteroConv(sum) conv layers, stacks of RGCNConv / FastRGCNConv on a
-typed-edge graph (and, with `attention=True`, GATConv),
+typed-edge graph (and, with `attention=True`, GATConv and GATv2Conv),
 each optionally followed by an elementwise activation, then Linear layers with activations (the
 layout of tests/test_utils.py:10-83 and the notebooks) — and lowers it to:
 
@@ -34,7 +34,7 @@ class UnsupportedArch(ValueError):
 
 @dataclass
 class Term:
-    kind: str          # "gcn" | "mean" | "sum" | "max" | "root" | "att" | "rel"
+    kind: str          # "gcn" | "mean" | "sum" | "max" | "root" | "att" | "rel" | "att2"
     rel: int           # relation index (ignored for root and rel)
     weight: torch.Tensor  # [f_out, f_in] (att: W_src, [heads * head_ch, f_in]; rel: [slices, f_out, f_in])
     dst_type: int = -1    # multi-node-type: destination node type of the relation
@@ -46,6 +46,12 @@ class Term:
     weight_dst: Optional[torch.Tensor] = None  # bipartite relations: W_dst; None: W_src for both ends
     neg_slope: float = 0.2
     self_loops: bool = False
+    # kind "att2" (GATv2Conv, PyG 2.0.4): one term per relation; weight = W_l, heads / head_ch /
+    # neg_slope / self_loops as for "att"
+    weight_r: Optional[torch.Tensor] = None    # W_r [heads * head_ch, f_in]; None: shared (W_l)
+    bias_l: Optional[torch.Tensor] = None      # lin_l.bias [heads * head_ch] (inside the messages)
+    bias_r: Optional[torch.Tensor] = None      # lin_r.bias
+    att: Optional[torch.Tensor] = None         # [heads, head_ch]
     # kind "rel" (RGCNConv / FastRGCNConv, PyG 2.0.4): one term per conv layer, over every edge
     # type of the graph.  Per relation r the mean (norm "mean": over that relation's kept in-edges,
     # 0 without one) or sum (norm "sum") A_r of the source rows; the term adds sum_s B_s weight[s]^T
@@ -117,6 +123,11 @@ def _is_gat(m):
         hasattr(m, a) for a in ("lin_src", "lin_dst", "att_src", "att_dst", "heads", "out_channels"))
 
 
+def _is_gatv2(m):
+    return type(m).__name__ == "GATv2Conv" and all(
+        hasattr(m, a) for a in ("lin_l", "lin_r", "att", "heads", "out_channels"))
+
+
 def _is_graphconv(m):
     return type(m).__name__ == "GraphConv" and hasattr(m, "lin_rel") and hasattr(m, "lin_root")
 
@@ -134,7 +145,7 @@ def _is_rgcn(m):
 
 def _is_conv(m, attention=False):
     return type(m).__name__ in ("GCNConv", "SAGEConv", "HeteroConv") or _is_graphconv(m) or _is_gin(m) \
-        or _is_rgcn(m) or (attention and _is_gat(m))
+        or _is_rgcn(m) or (attention and (_is_gat(m) or _is_gatv2(m)))
 
 
 def _is_linear(m):
@@ -144,6 +155,8 @@ def _is_linear(m):
 def _leaf_units(module, attention=False):
     """Registration-order walk yielding conv / linear / activation units (convs not entered)."""
     for child in module.children():
+        if _is_gatv2(child) and not attention:
+            raise UnsupportedArch("GATv2Conv without the attention opt-in (attention=True)")
         if _is_conv(child, attention) or _is_linear(child) or _act_name(child) is not None:
             yield child
         elif type(child).__name__ in _SKIP:
@@ -191,6 +204,38 @@ def _gat_terms(conv, rel, bipartite):
     return [term], b, None, W.shape[1], H * C
 
 
+def _gatv2_terms(conv, rel, bipartite):
+    """One GATv2Conv relation as an "att2" term: W_l / b_l (the messages), W_r / b_r (None when the
+    conv shares lin_l), att [heads, head_ch]; the conv's own bias is the layer's."""
+    H, C = int(conv.heads), int(conv.out_channels)
+    if not bool(getattr(conv, "concat", True)) and H > 1:
+        raise UnsupportedArch("GATv2Conv(concat=False) with several heads")
+    if getattr(conv, "edge_dim", None) is not None or getattr(conv, "lin_edge", None) is not None:
+        raise UnsupportedArch("GATv2Conv with edge_dim")
+    if (H * C + 31) // 32 * 32 > 256:
+        raise UnsupportedArch("GATv2Conv wider than 256 columns (heads * out_channels, padded to 32)")
+    if bipartite or not isinstance(getattr(conv, "in_channels", 0), int):
+        raise UnsupportedArch("GATv2Conv on a bipartite relation / with tuple in_channels")
+    if _lazy(conv.lin_l) or _lazy(conv.lin_r):
+        raise UnsupportedArch("GATv2Conv with uninitialised (lazy) weights")
+    shared = conv.lin_r is conv.lin_l
+    Wl = _f32(conv.lin_l.weight)
+    Wr = None if shared else _f32(conv.lin_r.weight)
+    if Wl.shape[0] != H * C or (Wr is not None and Wr.shape != Wl.shape):
+        raise UnsupportedArch("GATv2Conv weight shape does not match heads * out_channels")
+    if tuple(conv.att.shape)[-2:] != (H, C) or conv.att.numel() != H * C:
+        raise UnsupportedArch("GATv2Conv att shape does not match heads x out_channels")
+    bl = _f32(conv.lin_l.bias) if getattr(conv.lin_l, "bias", None) is not None else None
+    br = bl if shared else \
+        (_f32(conv.lin_r.bias) if getattr(conv.lin_r, "bias", None) is not None else None)
+    b = _f32(conv.bias) if getattr(conv, "bias", None) is not None else None
+    term = Term("att2", rel, Wl, heads=H, head_ch=C, weight_r=Wr, bias_l=bl, bias_r=br,
+                att=_f32(conv.att).reshape(H, C),
+                neg_slope=float(getattr(conv, "negative_slope", 0.2)),
+                self_loops=bool(getattr(conv, "add_self_loops", True)))
+    return [term], b, None, Wl.shape[1], H * C
+
+
 def fold_attention(term):
     """The attention vectors of an "att" term folded through its weights: (v_s, v_d), each
     [heads, f_in], with v_s[h] = W_src[hC:(h+1)C, :]^T att_src[h] (v_d likewise, with W_dst for
@@ -234,8 +279,9 @@ def stack_attention(terms, f_in_pad, f_out_pad):
 
 
 def _check_unmixed(terms):
-    if any(t.kind == "att" for t in terms) and not all(t.kind == "att" for t in terms):
-        raise UnsupportedArch("a conv layer mixing GATConv with GCNConv / SAGEConv relations")
+    for kind, name in (("att", "GATConv"), ("att2", "GATv2Conv")):
+        if any(t.kind == kind for t in terms) and not all(t.kind == kind for t in terms):
+            raise UnsupportedArch(f"a conv layer mixing {name} with other relations")
 
 
 _AGGR_KIND = {"mean": "mean", "add": "sum", "sum": "sum", "max": "max"}
@@ -343,6 +389,8 @@ def _single_conv_terms(conv, rel, attention=False, bipartite=False):
         raise UnsupportedArch(f"{name} inside HeteroConv")
     if attention and _is_gat(conv):
         return _gat_terms(conv, rel, bipartite)
+    if attention and _is_gatv2(conv):
+        return _gatv2_terms(conv, rel, bipartite)
     if name == "GCNConv":
         if getattr(conv, "improved", False) or not getattr(conv, "add_self_loops", True) \
                 or not getattr(conv, "normalize", True):
@@ -394,7 +442,8 @@ def _conv_layer(conv, rel_index, attention=False):
             if et[0] != et[-1]:
                 raise UnsupportedArch("bipartite relations need the multi-node-type path")
             t, b, wr, fi, fo = _single_conv_terms(sub, rel_index[et], attention)
-            if f_out is not None and fo != f_out and (t[0].kind == "att" or terms[0].kind == "att"):
+            if f_out is not None and fo != f_out and \
+                    (t[0].kind in ("att", "att2") or terms[0].kind in ("att", "att2")):
                 raise UnsupportedArch("HeteroConv relations with different output widths")
             terms += t
             if b is not None:
@@ -445,6 +494,8 @@ def _conv_layer_multi(conv, rel_index, node_type_names, attention=False):
         s_t, d_t = node_type_names.index(et[0]), node_type_names.index(et[-1])
         if type(sub).__name__ == "GCNConv" and s_t != d_t:
             raise UnsupportedArch("GCNConv on a bipartite relation")
+        if _is_gatv2(sub):
+            raise UnsupportedArch("GATv2Conv on a multi-node-type graph")
         t, b, wr, fi, fo = _single_conv_terms(sub, rel_index[et], attention, s_t != d_t)
         if t[0].kind == "att" and t[0].self_loops:
             raise UnsupportedArch("GATConv(add_self_loops=True) on a multi-node-type graph")
@@ -552,8 +603,8 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
     """Lower `arch` to a ModelProgram.  `edge_type_names` (list of (src, rel, dst) tuples in
     homogenised edge-type order, data.py:743-822) enables HeteroConv relations;
     `node_type_names` with two or more types selects the multi-node-type lowering.
-    `attention=True` (opt-in) also lowers GATConv relations, to "att" terms; by default an
-    arch with GATConv raises UnsupportedArch."""
+    `attention=True` (opt-in) also lowers GATConv relations, to "att" terms, and GATv2Conv
+    relations, to "att2" terms; by default an arch with either raises UnsupportedArch."""
     if type(arch).__name__ == "LinkModel" and hasattr(arch, "encoder"):
         prog = compile_arch(arch.encoder, edge_type_names, node_type_names, attention)
         if prog.pool is not None:
@@ -630,6 +681,6 @@ def count_message_passing(arch: nn.Module) -> int:
     for m in arch.modules():
         if any(c.__name__ == "MessagePassing" for c in type(m).__mro__):
             n += 1
-        elif type(m).__name__ in ("GCNConv", "SAGEConv", "GATConv", "GINConv", "GraphConv") + _RGCN_NAMES:
+        elif type(m).__name__ in ("GCNConv", "SAGEConv", "GATConv", "GATv2Conv", "GINConv", "GraphConv") + _RGCN_NAMES:
             n += 1
     return n

@@ -39,7 +39,8 @@
  *                                        decoder (GCN / SAGE-mean terms, or RGCN REL terms, v27)
  *                                        (v27 addendum, no version change: xpg_layer_desc.pool
  *                                        appended; a conv stack followed by a global mean / add /
- *                                        max readout and a dense head, one output per mask row)
+ *                                        max readout and a dense head, one output per mask row;
+ *                                        XPG_TERM_ATT2 = 7: GATv2Conv layers, enum xpg_term below)
  *   xpg_pool_rows / _workspace / _describe — the readout alone (PyG global_mean_pool /
  *                                        global_add_pool / global_max_pool over one graph per row)
  *   xpg_forward_describe / xpg_wide_variants — none: host queries of xpg_masked_forward's own
@@ -80,7 +81,34 @@ enum xpg_term { XPG_TERM_GCN = 0,   /* D^-1/2 (A_r + I) D^-1/2 over relation r  
                 XPG_TERM_ATT = 3,   /* graph attention over relation r (GATConv, v22; below)  */
                 XPG_TERM_SUM = 4,   /* sum over kept in-edges of relation r (v25; below)      */
                 XPG_TERM_MAX = 5,   /* element-wise max over kept in-edges (v25; below)       */
-                XPG_TERM_REL = 6    /* every relation's mean / sum, one term (RGCN, v26; below) */ };
+                XPG_TERM_REL = 6,   /* every relation's mean / sum, one term (RGCN, v26; below) */
+                XPG_TERM_ATT2 = 7   /* dynamic attention over relation r (GATv2Conv; v27 addendum, below) */ };
+/* ATT2 (v27 addendum: an enum value only; the version, every struct layout and the meaning of
+ * every existing plan are unchanged).  One term = one GATv2Conv relation (PyG 2.0.4) and reuses
+ * xpg_term_desc's fields: rel, heads, head_ch, neg_slope and self_loops mean what they mean for
+ * ATT, and the edge set of target t in mask row b is exactly ATT's (xpg_term_desc below; the
+ * loop's source row is XL[t]).  dst_type must be -1 and the layer's tgt_type NULL; node masks only.
+ * With XL = lin_l(x), XR = lin_r(x) viewed as [.][heads][head_ch], edge e = (u -> t), head h:
+ *   z_e^h = sum_c att[h][c] * leaky_relu(XL[u][h][c] + XR[t][h][c], neg_slope),
+ *   m = max z, p_e = exp(z_e - m), alpha_e = p_e / (sum p + 1e-16), an empty edge set gives 0,
+ * and the term adds sum_e alpha_e^h XL[u][h * head_ch + c] to column h * head_ch + c (the lin_l
+ * bias travels inside the messages).  A layer's terms are all ATT2 or none and are summed; then
+ * the layer's bias and act apply; columns past f_out are 0.  The layer is transform-then-aggregate
+ * at every depth, so its `weight` is NULL and no dense launch follows it.
+ * att_src, at every depth: device [f_out_pad], att[h][c] at h * head_ch + c, 0 past heads * head_ch.
+ * Layer 1: table = XL [n0][f_out_pad] = X[F_0] W_l^T + b_l, att_dst = XR [n0][f_out_pad] (may alias
+ * table: share_weights); padded columns 0; built once per plan (features are never masked).
+ * Layer >= 2: table = device [2][f_out_pad][f_in_pad], W_l then W_r, zero-padded; coef = device
+ * [2][f_out_pad], b_l then b_r (zeros without a bias); att_dst = NULL.  n_slices == 1 marks shared
+ * weights: table / coef then hold the one block [1][f_out_pad][f_in_pad] / [1][f_out_pad] and XR is
+ * XL (any other n_slices: the two blocks).  The forward transforms every previous-frontier row
+ * of the call with xpg_dense's kernel into its workspace, then aggregates.
+ * Refused before any launch (XPG_EINVAL, from xpg_masked_forward, xpg_forward_workspace and
+ * xpg_forward_describe alike, without reading a device pointer): ATT2 mixed with another kind in a
+ * layer, edge_masks, tgt_type or dst_type != -1, heads * head_ch > f_out_pad, a missing att_src /
+ * table (att_dst at layer 1, coef at deeper layers), a non-NULL layer weight (at layer 1: the raw
+ * form).  ATT2 plans run on the multi-kernel path only (xpg_forward_describe: `unfused`), launch no
+ * degree pass unless another layer needs one, and need no score region. */
 /* SUM and MAX (v25; node masks only: a plan with edge_masks set and one of them is refused).  The
  * edge set of target t in mask row b for relation r is MEAN's: every CSR in-edge (u -> t) with
  * bit(b, u) & bit(b, t), duplicate edges as separate entries, plus self_mult[r][t] copies of

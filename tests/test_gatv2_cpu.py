@@ -1,0 +1,343 @@
+"""GATv2Conv without a GPU: nn.GATv2Conv against the fp64 restatement of tests/gatv2_ref.py, the
+"att2" lowering of program.compile_arch(..., attention=True) and its refusals, the host side of
+the C-ABI (XPG_TERM_ATT2: host checks, dispatch, workspace) on synthetic descriptors whose device
+pointers are only tested for NULL, and the sensitivity conditions of the GPU parity inputs
+(tests/test_gpu_gatv2.py), asserted on the reference alone."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import gatv2_ref
+from test_dispatch_cpu import PTR, describe, make_plan, variants
+
+from bikg_graph_explainability_public_amd import _lib, nn as xnn
+from bikg_graph_explainability_public_amd.program import (UnsupportedArch, compile_arch,
+                                                          count_message_passing)
+
+ENV = ("XPG_FORWARD", "XPG_FORWARD_STRICT", "XPG_DIAGNOSTICS")
+
+
+@pytest.fixture(autouse=True)
+def _clean_env(monkeypatch):
+    for k in ENV:
+        monkeypatch.delenv(k, raising=False)
+
+
+# ------------------------------------------------------------------ module vs the restatement
+def _conv_case(seed=3):
+    """The hub graph, plus node 11 stripped of every in-edge (self-loops included)."""
+    S = 400
+    ei = gatv2_ref.hub_graph(S)
+    ei = ei[:, ei[1] != 11]
+    x = torch.randn((S, 6), generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
+    return x, ei
+
+
+@pytest.mark.parametrize("kw", [
+    {}, {"add_self_loops": False}, {"share_weights": True},
+    {"share_weights": True, "add_self_loops": False}, {"bias": False},
+    {"heads": 1, "concat": False}, {"negative_slope": 0.0}, {"negative_slope": 1.0},
+    {"heads": 3, "add_self_loops": False, "bias": False},
+])
+def test_module_matches_restatement_fp64(kw):
+    x, ei = _conv_case()
+    torch.manual_seed(5)
+    args = dict(heads=2)
+    args.update(kw)
+    conv = xnn.GATv2Conv(6, 5, **args).double().eval()
+    with torch.no_grad():
+        if conv.bias is not None:
+            conv.bias.uniform_(-1, 1)
+        if conv.lin_l.bias is not None:
+            conv.lin_l.bias.uniform_(-1, 1)
+            conv.lin_r.bias.uniform_(-1, 1)
+        got = conv(x, torch.as_tensor(ei)).numpy()
+    ref = gatv2_ref.gatv2_conv(x.numpy(), ei[0], ei[1], gatv2_ref.conv_params(conv))
+    assert got.shape == ref.shape == (400, 5 * (args["heads"] if args.get("concat", True) else 1))
+    assert np.abs(got - ref).max() < 1e-12
+    if not args.get("add_self_loops", True):  # no in-edge, no added loop: exactly the bias
+        want = 0 if conv.bias is None else conv.bias.detach().numpy()
+        assert np.abs(got[11] - want).max() == 0
+
+
+def test_state_dict_keys_and_hops():
+    conv = xnn.GATv2Conv(6, 5, heads=2)
+    assert set(conv.state_dict()) == {"lin_l.weight", "lin_l.bias", "lin_r.weight", "lin_r.bias",
+                                      "att", "bias"}
+    assert tuple(conv.att.shape) == (1, 2, 5) and tuple(conv.bias.shape) == (10,)
+    assert tuple(xnn.GATv2Conv(6, 5, heads=1, concat=False).bias.shape) == (5,)
+    shared = xnn.GATv2Conv(6, 5, heads=2, share_weights=True)
+    assert shared.lin_r is shared.lin_l
+    other = xnn.GATv2Conv(6, 5, heads=2)
+    other.load_state_dict(conv.state_dict())
+    assert torch.equal(other.lin_r.weight, conv.lin_r.weight)
+    arch = xnn.ConvStack("gatv2", [16, 8, 8], [8, 1], heads=[2, 1], share_weights=True)
+    assert count_message_passing(arch) == 2 and isinstance(arch.conv[0], xnn.MessagePassing)
+    assert arch.conv[2].in_channels == 16 and arch.conv[2].lin_r is arch.conv[2].lin_l
+    assert not xnn.ConvStack("gatv2", [4, 4], [4, 1], add_self_loops=False).conv[0].add_self_loops
+    with pytest.raises(ValueError):
+        xnn.ConvStack("sage", [4, 4], [4, 1], share_weights=True)
+    rels = [("n", "a", "n"), ("n", "b", "n")]
+    het = xnn.ConvStack("gatv2", [4, 4], [4, 1], hetero_rels=rels)
+    assert isinstance(het.conv[0], xnn.HeteroConv) and len(het.conv[0].convs) == 2
+    assert isinstance(het.conv[0].convs["n__a__n"], xnn.GATv2Conv)
+
+
+# ------------------------------------------------------------------ lowering
+class One(torch.nn.Module):
+    def __init__(self, conv, width=8):
+        super().__init__()
+        self.conv = torch.nn.ModuleList([conv, torch.nn.ReLU()])
+        self.fc = torch.nn.ModuleList([xnn.Linear(width, 1), torch.nn.Sigmoid()])
+
+
+def test_lowering_term_fields():
+    torch.manual_seed(0)
+    arch = xnn.ConvStack("gatv2", [16, 8, 8], [8, 1], heads=[2, 1], add_self_loops=False).eval()
+    with torch.no_grad():
+        arch.conv[0].bias.uniform_(-1, 1)
+        arch.conv[0].lin_l.bias.uniform_(-1, 1)
+    prog = compile_arch(arch, attention=True)
+    assert [(c.f_in, c.f_out, c.act) for c in prog.convs] == [(16, 16, "relu"), (16, 8, "relu")]
+    for c, conv, H in zip(prog.convs, (arch.conv[0], arch.conv[2]), (2, 1)):
+        (t,) = c.terms
+        assert (t.kind, t.rel, t.dst_type, t.heads, t.head_ch) == ("att2", 0, -1, H, 8)
+        assert t.neg_slope == 0.2 and t.self_loops is False
+        assert torch.equal(t.weight, conv.lin_l.weight) and torch.equal(t.weight_r, conv.lin_r.weight)
+        assert torch.equal(t.bias_l, conv.lin_l.bias) and torch.equal(t.bias_r, conv.lin_r.bias)
+        assert torch.equal(t.att, conv.att.reshape(H, 8))
+        assert torch.equal(c.bias, conv.bias)
+    shared = compile_arch(One(xnn.GATv2Conv(16, 8, share_weights=True, bias=False)), attention=True)
+    (t,) = shared.convs[0].terms
+    assert t.weight_r is None and t.bias_l is None and t.bias_r is None and t.self_loops is True
+    assert not shared.convs[0].bias.any()
+    compile_arch(One(xnn.GATv2Conv(16, 8, heads=1, concat=False)), attention=True)
+    rels = [("n", "a", "n"), ("n", "b", "n")]
+    both = compile_arch(xnn.ConvStack("gatv2", [16, 8], [8, 1], hetero_rels=rels), rels, attention=True)
+    assert [(t.kind, t.rel) for t in both.convs[0].terms] == [("att2", 0), ("att2", 1)]
+    mix = torch.nn.Module()
+    mix.conv = torch.nn.ModuleList([xnn.GCNConv(16, 8), torch.nn.ReLU(), xnn.GATv2Conv(8, 4, heads=2),
+                                    torch.nn.ReLU()])
+    mix.fc = torch.nn.ModuleList([xnn.Linear(8, 1), torch.nn.Sigmoid()])
+    assert [c.terms[0].kind for c in compile_arch(mix, attention=True).convs] == ["gcn", "att2"]
+    pooled = xnn.PooledModel(xnn.ConvStack("gatv2", [16, 8], [8]), "mean", [8, 1])
+    prog = compile_arch(pooled, attention=True)
+    assert prog.pool == "mean" and prog.convs[0].terms[0].kind == "att2"
+
+
+def test_opt_in_and_refusals():
+    arch = xnn.ConvStack("gatv2", [16, 8, 8], [8, 1], heads=[2, 1])
+    for kw in ({}, {"attention": False}):
+        with pytest.raises(UnsupportedArch):
+            compile_arch(arch, **kw)
+    with pytest.raises(UnsupportedArch):  # also behind another conv kind
+        mix = torch.nn.Module()
+        mix.conv = torch.nn.ModuleList([xnn.GCNConv(16, 8), torch.nn.ReLU(), xnn.GATv2Conv(8, 8)])
+        mix.fc = torch.nn.ModuleList([xnn.Linear(8, 1)])
+        compile_arch(mix)
+    with pytest.raises(UnsupportedArch, match="several heads"):
+        compile_arch(One(xnn.GATv2Conv(16, 8, heads=2, concat=False)), attention=True)
+    conv = xnn.GATv2Conv(16, 8)
+    conv.edge_dim = 3
+    with pytest.raises(UnsupportedArch, match="edge_dim"):
+        compile_arch(One(conv), attention=True)
+    conv = xnn.GATv2Conv(16, 8)
+    conv.lin_edge = xnn.Linear(3, 8)
+    with pytest.raises(UnsupportedArch, match="edge_dim"):
+        compile_arch(One(conv), attention=True)
+    conv = xnn.GATv2Conv(16, 8)
+    conv.lin_r = xnn.Linear(-1, 8)
+    with pytest.raises(UnsupportedArch, match="lazy"):
+        compile_arch(One(conv), attention=True)
+    conv = xnn.GATv2Conv(16, 8)
+    conv.in_channels = (16, 16)
+    with pytest.raises(UnsupportedArch, match="tuple in_channels"):
+        compile_arch(One(conv), attention=True)
+    mrels = [("A", "ab", "B"), ("B", "ba", "A")]
+    het = One(xnn.HeteroConv({r: xnn.GATv2Conv(16, 8, add_self_loops=False) for r in mrels}))
+    with pytest.raises(UnsupportedArch):  # bipartite relation on the single-type lowering
+        compile_arch(het, mrels, attention=True)
+    with pytest.raises(UnsupportedArch, match="multi-node-type"):
+        compile_arch(het, mrels, ["A", "B"], attention=True)
+    same = [("A", "aa", "A"), ("B", "bb", "B")]
+    het = One(xnn.HeteroConv({r: xnn.GATv2Conv(16, 8, add_self_loops=False) for r in same}))
+    with pytest.raises(UnsupportedArch, match="multi-node-type"):
+        compile_arch(het, same, ["A", "B"], attention=True)
+    rels = [("n", "a", "n"), ("n", "b", "n")]
+    for other in (xnn.SAGEConv(16, 8), xnn.GATConv(16, 8)):
+        mixed = One(xnn.HeteroConv({rels[0]: xnn.GATv2Conv(16, 8), rels[1]: other}))
+        with pytest.raises(UnsupportedArch, match="mixing"):
+            compile_arch(mixed, rels, attention=True)
+    with pytest.raises(UnsupportedArch, match="256"):
+        compile_arch(One(xnn.GATv2Conv(16, 65, heads=4), 260), attention=True)
+    compile_arch(One(xnn.GATv2Conv(16, 64, heads=4), 256), attention=True)
+
+
+# ------------------------------------------------------------------ descriptors (host only)
+ATT2, SAGE, GCN = ("att2",), ("mean", "root"), ("gcn",)
+
+
+def _att2_plan(layers=((ATT2, 16), (ATT2, 8)), heads=(1,), hc=((2, 8), (1, 8)), **kw):
+    """make_plan's descriptor with the ATT2 layers filled in as the header describes them."""
+    desc = make_plan(list(layers), heads, **kw)
+    for li, (ld, (kinds, _)) in enumerate(zip(desc._keep[0], layers)):
+        if "att2" not in kinds:
+            continue
+        ld.weight = None
+        for k in range(len(kinds)):
+            t = ld.terms[k]
+            t.heads, t.head_ch = hc[li]
+            t.neg_slope, t.self_loops = 0.2, 1
+            t.table, t.att_src = PTR, PTR
+            t.att_dst = PTR if li == 0 else None
+            t.coef = None if li == 0 else PTR
+    return desc
+
+
+def _ws(desc, rows=70):
+    n = ctypes.c_size_t(0)
+    _lib.check(_lib.load().xpg_forward_workspace(ctypes.byref(desc), rows, ctypes.byref(n)))
+    return n.value
+
+
+def _refused(desc, msg):
+    lib = _lib.load()
+    n = ctypes.c_size_t(0)
+    buf = ctypes.create_string_buffer(256)
+    for rc in (lib.xpg_forward_workspace(ctypes.byref(desc), 70, ctypes.byref(n)),
+               lib.xpg_forward_describe(ctypes.byref(desc), 70, buf, 256),
+               lib.xpg_masked_forward(ctypes.byref(desc), None, 70, None, None, 1 << 40, None)):
+        assert rc == 1  # XPG_EINVAL: no pointer was read, nothing launched
+        assert msg in lib.xpg_last_error().decode()
+
+
+def test_abi_is_unchanged():
+    assert _lib.TERM["att2"] == 7 and _lib.ABI_VERSION == 27
+    assert [f[0] for f in _lib.LayerDesc._fields_][-2:] == ["seg_rel", "pool"]
+    assert _lib.ForwardPlanDesc._fields_[-1][0] == "dot_scale"
+    assert {k: v for k, v in _lib.TERM.items() if k != "att2"} == \
+        {"gcn": 0, "mean": 1, "root": 2, "att": 3, "sum": 4, "max": 5, "rel": 6}
+    assert len(variants()) == 27
+
+
+def test_host_checks():
+    d = _att2_plan(layers=(((("att2", "mean")), 16), (ATT2, 8)))
+    d._keep[0][0].terms[1].table = PTR
+    _refused(d, "ATT2 terms cannot be mixed with other kinds")
+    d = _att2_plan(layers=((ATT2, 16), (("att2", "att"), 8)))
+    _refused(d, "ATT2 terms cannot be mixed with other kinds")
+    d = _att2_plan()
+    d.edge_masks = 1
+    _refused(d, "edge-mask plans (edge_masks)")
+    d = _att2_plan()
+    d._keep[0][1].tgt_type = PTR
+    _refused(d, "multi-node-type plans (tgt_type)")
+    d = _att2_plan()
+    d._keep[0][0].terms[0].dst_type = 0
+    _refused(d, "dst_type must be -1")
+    d = _att2_plan(hc=((2, 17), (1, 8)))
+    _refused(d, "heads * head_ch must fit")
+    d = _att2_plan(hc=((2, 8), (0, 8)))
+    _refused(d, "heads * head_ch must fit")
+    for li, field, msg in ((0, "att_src", "missing att_src or table"), (1, "att_src", "missing att_src or table"),
+                           (0, "table", "missing att_src or table"), (1, "table", "missing att_src or table"),
+                           (0, "att_dst", "layer 1 needs att_dst"), (1, "coef", "deeper layer needs coef")):
+        d = _att2_plan()
+        setattr(d._keep[0][li].terms[0], field, None)
+        _refused(d, msg)
+    d = _att2_plan()
+    d._keep[0][1].weight = PTR
+    _refused(d, "weight must be NULL")
+    d = _att2_plan()
+    d._keep[0][0].weight, d._keep[0][0].f_in_pad = PTR, 32
+    _refused(d, "does not take the raw form")
+    d = _att2_plan()
+    d._keep[0][1].f_in_pad = 64
+    _refused(d, "f_in_pad must equal previous f_out_pad")
+
+
+@pytest.mark.parametrize("kw", [{}, {"n_nodes": 10000, "n_tgt": 10000}, {"n_nodes": 40, "n_tgt": 8}])
+def test_att2_plans_take_the_multi_kernel_path(kw, monkeypatch):
+    for layers in (((ATT2, 16), (ATT2, 8)), ((GCN, 32), (ATT2, 32)), ((ATT2, 32), (SAGE, 32))):
+        desc = _att2_plan(layers=layers, hc=((2, 8), (1, 8)), **kw)
+        assert describe(desc) == "unfused"
+        for forced in ("rows", "fused", "wide"):
+            monkeypatch.setenv("XPG_FORWARD", forced)
+            monkeypatch.delenv("XPG_FORWARD_STRICT", raising=False)
+            assert describe(desc) == "unfused"
+            monkeypatch.setenv("XPG_FORWARD_STRICT", "1")
+            with pytest.raises(RuntimeError, match="forced XPG_FORWARD path does not take this plan"):
+                describe(desc)
+            rc = _lib.load().xpg_masked_forward(ctypes.byref(desc), None, 70, None, None, 1 << 40, None)
+            assert rc == 1 and b"does not take this plan" in _lib.load().xpg_last_error()
+        monkeypatch.delenv("XPG_FORWARD")
+        monkeypatch.delenv("XPG_FORWARD_STRICT")
+
+
+def test_workspace_of_att2_plans():
+    """Per layer the output rows; per ATT2 layer past the first the XL | XR region (rows * n_prev *
+    2 * n_terms * f_out_pad floats, the largest); no dense-input and no score region for them."""
+    up = lambda b: (b + 255) // 256 * 256
+    rows, n = 70, 300
+    fixed = up(4 * rows * n) + 2 * up(4 * rows * n * 32) + up(4 * 32)  # degrees, two head buffers, counters
+    got = _ws(_att2_plan(), rows)
+    assert got == fixed + 2 * up(4 * rows * n * 32) + up(4 * rows * n * 2 * 32)
+    two = _att2_plan(layers=((ATT2, 16), (("att2", "att2"), 40)), hc=((2, 8), (1, 40)))
+    assert _ws(two, rows) == fixed + up(4 * rows * n * 32) + up(4 * rows * n * 64) + up(4 * rows * n * 4 * 64)
+    first = _att2_plan(layers=((ATT2, 32), (SAGE, 32)))
+    plain = make_plan([(SAGE, 32), (SAGE, 32)])
+    assert _ws(first, rows) == _ws(plain, rows)  # an ATT2 first layer adds no region
+
+
+# xpg_forward_workspace(rows = 70) of descriptors without ATT2 terms, recorded from the library built
+# at the parent commit b98475f: this change must leave every one of them byte-identical.
+PARENT_WS = {
+    "gcn": 1803520, "sage_wide": 340640768, "att": 13692672, "rel": 26880256, "pooled": 59385088,
+    "sage_heads": 37716480,
+}
+
+
+def _parent_cases():
+    gcn = make_plan([(GCN, 32), (GCN, 32)], n_nodes=40, n_tgt=40)
+    sage_wide = make_plan([(SAGE, 128), (SAGE, 128)], n_nodes=10000, n_tgt=10000)
+    att = make_plan([(("att",), 16), (("att",), 8)])
+    for li, ld in enumerate(att._keep[0]):
+        t = ld.terms[0]
+        t.heads, t.head_ch = (2, 8) if li == 0 else (1, 8)
+        t.att_src = t.att_dst = PTR
+    rel = make_plan([(("rel", "root"), 64), (("rel", "root"), 64)])
+    for li, ld in enumerate(rel._keep[0]):
+        ld.terms[0].n_slices, ld.terms[0].rel, ld.seg_ptr, ld.seg_rel = 1, -1, PTR, PTR
+    pooled = make_plan([(SAGE, 64), (SAGE, 96)], (8, 1), n_nodes=600, n_tgt=600)
+    pooled._keep[0][1].pool = 2
+    sage_heads = make_plan([(SAGE, 64), (("mean", "root", "root"), 96), (SAGE, 32)], (16, 1))
+    return {"gcn": gcn, "sage_wide": sage_wide, "att": att, "rel": rel, "pooled": pooled,
+            "sage_heads": sage_heads}
+
+
+def test_other_plans_keep_their_workspace_size():
+    got = {k: _ws(d) for k, d in _parent_cases().items()}
+    print(got)
+    assert got == PARENT_WS
+
+
+# ------------------------------------------------------------------ the GPU cases' sensitivity
+@pytest.mark.parametrize("att_scale", [1.0, 16.0])
+@pytest.mark.parametrize("self_loops", [False, True])
+def test_gpu_cases_are_sensitive(self_loops, att_scale):
+    """From the fp64 reference alone, for the inputs tests/test_gpu_gatv2.py uses: at least half of
+    the 64 rows more than 1e-3 (100 x the GPU bar) from the all-on row, at least a third of the
+    64 x 3 outputs more than 1e-3 from the same model under uniform attention (att = 0), and every
+    output off the sigmoid's tails.  A kernel that ignores the masks, or the logits, cannot pass."""
+    c = gatv2_ref.hub_case(self_loops, att_scale)
+    ref, uni, m = c["ref"], c["uniform"], c["masks"]
+    assert ref.shape == uni.shape == (64, 3) and m[1].all() and not m[0].any()
+    assert not m[2, 0] and not m[3, 7] and not m[4, 399]
+    moved = (np.abs(ref - ref[1]) > 1e-3).any(1).sum()
+    dyn = (np.abs(ref - uni) > 1e-3).sum()
+    print("rows off the all-on row:", moved, "outputs off uniform attention:", dyn)
+    assert moved >= 32
+    assert dyn >= 64
+    assert ((ref > 0.02) & (ref < 0.98)).all()

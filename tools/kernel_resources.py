@@ -25,4 +25,5 @@ for name, d in rows.items():
         dn = dn.split("(")[0]
         print(f"{dn[:80]:80s} vgpr={d.get('VGPRs','?'):>4} agpr={d.get('AGPRs','?'):>3} "
               f"sgpr={d.get('SGPRs','?'):>3} vspill={d.get('VGPRs Spill','?')} "
+              f"scratch={d.get('ScratchSize [bytes/lane]','?')} "
               f"lds={d.get('LDS Size [bytes/block]','?')} occ={d.get('Occupancy [waves/SIMD]','?')}")
