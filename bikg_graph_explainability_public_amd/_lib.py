@@ -18,6 +18,7 @@ ACT = {None: 0, "identity": 0, "relu": 1, "sigmoid": 2, "tanh": 3, "leaky_relu":
 TERM = {"gcn": 0, "mean": 1, "root": 2, "att": 3, "sum": 4, "max": 5, "rel": 6, "att2": 7}
 REL_NORM = {"mean": 0, "sum": 1}
 POOL = {None: 0, "mean": 1, "sum": 2, "max": 3}
+NORM = {None: 0, "layer": 1}
 
 c_i32, c_i64, c_f32, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -63,6 +64,12 @@ class ForwardPlanDesc(ctypes.Structure):
                 ("dot_b", c_i32), ("dot_act", c_i32), ("dot_scale", c_vp)]
 
 
+class PostDesc(ctypes.Structure):
+    """xpg_post_desc (v27 addendum): one conv layer's post-op; all zero = none."""
+    _fields_ = [("norm", c_i32), ("eps", c_f32), ("scale", c_vp), ("shift", c_vp), ("gamma", c_vp),
+                ("beta", c_vp), ("act", c_i32), ("residual", c_i32)]
+
+
 class WlmParams(ctypes.Structure):
     _fields_ = [("lr", c_f32), ("l1_lambda", c_f32), ("beta1", c_f32), ("beta2", c_f32),
                 ("eps", c_f32), ("weight_decay", c_f32)]
@@ -106,6 +113,16 @@ _SIGS = {
     "xpg_pool_workspace": ([c_i64, c_i64, c_i64, ctypes.POINTER(ctypes.c_size_t)], c_i32),
     "xpg_pool_rows": ([c_vp, c_i64, c_i64, c_i64, c_i32, c_vp, c_vp, ctypes.c_size_t, c_vp], c_i32),
     "xpg_pool_describe": ([c_i64, c_i64, c_i64, c_i32, ctypes.c_char_p, ctypes.c_size_t], c_i32),
+    "xpg_forward_workspace_post": ([ctypes.POINTER(ForwardPlanDesc), ctypes.POINTER(PostDesc), c_i64,
+                                    ctypes.POINTER(ctypes.c_size_t)], c_i32),
+    "xpg_masked_forward_post": ([ctypes.POINTER(ForwardPlanDesc), ctypes.POINTER(PostDesc), c_vp, c_i64,
+                                 c_vp, c_vp, ctypes.c_size_t, c_vp], c_i32),
+    "xpg_forward_describe_post": ([ctypes.POINTER(ForwardPlanDesc), ctypes.POINTER(PostDesc), c_i64,
+                                   ctypes.c_char_p, ctypes.c_size_t], c_i32),
+    "xpg_post_rows": ([c_vp, c_i64, c_i64, c_i64, ctypes.POINTER(PostDesc), c_vp, c_i64, c_i64, c_i64,
+                       c_vp, c_vp], c_i32),
+    "xpg_post_describe": ([c_i64, c_i64, c_i64, ctypes.POINTER(PostDesc), ctypes.c_char_p,
+                           ctypes.c_size_t], c_i32),
     "xpg_profile_enable": ([ctypes.c_int], c_i32),
     "xpg_profile_read": ([c_vp, c_vp, c_i32], c_i32),
     "xpg_wlm_workspace": ([c_i64, c_i64, c_i64, c_i64, ctypes.POINTER(ctypes.c_size_t)], c_i32),

@@ -6384,8 +6384,201 @@ int launch_pool(const float* h, int64_t rows, int64_t n, int64_t ld, int kind, f
   return XPG_OK;
 }
 
+// ------------------------------------------------------------------------------------ post-op
+// A conv layer's post-op (xpg_post_desc, xpg_post_rows; the rules are in xpgnn.h), in place on the
+// layer's output rows h [M][ld], M = rows * n_tgt.  An item is one row on a group of G lanes, G the
+// power of two >= ld / 4 (at most 64), lane c of the group holding the row's float4 chunk c (lanes
+// past ld / 4 hold none: they load and store nothing and add 0 to the sums); a wave works on 64 / G
+// rows at once.  LayerNorm's two sums (mean, then the squared deviations) go across the group by an
+// xor butterfly, so every lane of a group ends with the same value, summed in one fixed order that
+// depends on (f_out, ld) alone: no LDS, no atomics.  Every lane of a wave stays in the loop (its
+// trip count is block-uniform) and rows past M are masked, so each shuffle reads a live lane.
+constexpr int kPostWaves = 4;
+
+struct PostArgs {
+  float* h;
+  int64_t M;
+  int ld, f_out, group;  // group: lanes per row, a power of two in 1..64
+  float eps;
+  const float *scale, *shift, *gamma, *beta;
+  int act;
+  const float* hprev;  // RES only
+  int ld_prev, n_tgt, n_prev;
+  const int32_t* tgt_prev;
+};
+
+__device__ __forceinline__ float post_group_sum(float s, int group) {
+  for (int m = 1; m < group; m <<= 1) s += __shfl_xor(s, m, 64);
+  return s;
+}
+
+template <int NORM, bool RES>
+__global__ __launch_bounds__(64 * kPostWaves) void k_post(const PostArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int per_wave = 64 / a.group;
+  const int c = lane & (a.group - 1);
+  const int col = 4 * c;
+  const bool chunk = col < a.ld;
+  const int64_t per_block = (int64_t)kPostWaves * per_wave;
+  const float4 one = make_float4(1.f, 1.f, 1.f, 1.f), zero = make_float4(0.f, 0.f, 0.f, 0.f);
+  const float4 sc = a.scale && chunk ? *reinterpret_cast<const float4*>(a.scale + col) : one;
+  const float4 sh = a.shift && chunk ? *reinterpret_cast<const float4*>(a.shift + col) : zero;
+  const float4 ga = NORM && a.gamma && chunk ? *reinterpret_cast<const float4*>(a.gamma + col) : one;
+  const float4 be = NORM && a.beta && chunk ? *reinterpret_cast<const float4*>(a.beta + col) : zero;
+  const bool r0 = col < a.f_out, r1 = col + 1 < a.f_out, r2 = col + 2 < a.f_out, r3 = col + 3 < a.f_out;
+  for (int64_t base = (int64_t)blockIdx.x * per_block; base < a.M; base += (int64_t)gridDim.x * per_block) {
+    const int64_t m = base + wave * per_wave + lane / a.group;
+    const bool live = chunk && m < a.M;
+    float4* hp = reinterpret_cast<float4*>(a.h + m * a.ld + col);
+    const float4 in = live ? *hp : zero;
+    // padded columns are never read as values (a select, not a product: they may hold anything)
+    float v0 = r0 ? fmaf(in.x, sc.x, sh.x) : 0.f;
+    float v1 = r1 ? fmaf(in.y, sc.y, sh.y) : 0.f;
+    float v2 = r2 ? fmaf(in.z, sc.z, sh.z) : 0.f;
+    float v3 = r3 ? fmaf(in.w, sc.w, sh.w) : 0.f;
+    if (NORM == XPG_NORM_LAYER) {
+      const float inv_n = 1.f / static_cast<float>(a.f_out);
+      const float mean = post_group_sum((v0 + v1) + (v2 + v3), a.group) * inv_n;
+      const float d0 = r0 ? v0 - mean : 0.f, d1 = r1 ? v1 - mean : 0.f;
+      const float d2 = r2 ? v2 - mean : 0.f, d3 = r3 ? v3 - mean : 0.f;
+      const float var = post_group_sum((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3), a.group) * inv_n;
+      const float r = 1.f / sqrtf(var + a.eps);
+      v0 = fmaf(d0 * r, ga.x, be.x);
+      v1 = fmaf(d1 * r, ga.y, be.y);
+      v2 = fmaf(d2 * r, ga.z, be.z);
+      v3 = fmaf(d3 * r, ga.w, be.w);
+    }
+    v0 = act_apply(v0, a.act);
+    v1 = act_apply(v1, a.act);
+    v2 = act_apply(v2, a.act);
+    v3 = act_apply(v3, a.act);
+    if (RES && live) {
+      const int64_t row = m / a.n_tgt;
+      const int t = static_cast<int>(m - row * a.n_tgt);
+      const float4 p = *reinterpret_cast<const float4*>(a.hprev + (row * a.n_prev + a.tgt_prev[t]) * a.ld_prev + col);
+      v0 += p.x;
+      v1 += p.y;
+      v2 += p.z;
+      v3 += p.w;
+    }
+    if (live) *hp = make_float4(r0 ? v0 : 0.f, r1 ? v1 : 0.f, r2 ? v2 : 0.f, r3 ? v3 : 0.f);
+  }
+}
+
+// a record that asks for nothing: the layer has no post-op
+bool post_any(const xpg_post_desc& q) {
+  return q.norm != XPG_NORM_NONE || q.scale || q.shift || q.gamma || q.beta || q.act != XPG_ACT_NONE || q.residual;
+}
+// the checks of one record that need no plan (xpg_post_rows and post_plan_check share them)
+int post_desc_check(const xpg_post_desc& q) {
+  XPG_REQ(q.norm == XPG_NORM_NONE || q.norm == XPG_NORM_LAYER, "post: norm outside enum xpg_norm");
+  XPG_REQ(q.norm != XPG_NORM_LAYER || (std::isfinite(q.eps) && q.eps > 0.f),
+          "post: LAYER norm needs a finite eps > 0");
+  XPG_REQ(q.norm == XPG_NORM_LAYER || (!q.gamma && !q.beta), "post: gamma / beta need norm LAYER");
+  XPG_REQ(q.act >= XPG_ACT_NONE && q.act <= XPG_ACT_ELU, "post: act outside enum xpg_act");
+  XPG_REQ(q.residual == 0 || q.residual == 1, "post: residual must be 0 or 1");
+  return XPG_OK;
+}
+// The one selection behind launch_post and the describe texts.
+const char* post_kernel_name(const xpg_post_desc& q) {
+  static const char* const names[] = {"k_post<none,0>", "k_post<none,1>", "k_post<layer,0>", "k_post<layer,1>"};
+  return names[(q.norm == XPG_NORM_LAYER ? 2 : 0) + (q.residual ? 1 : 0)];
+}
+int post_group(int64_t ld) {
+  int g = 1;
+  while (4 * g < ld) g <<= 1;
+  return g;
+}
+int post_shape_check(int64_t M, int64_t ld, int64_t f_out) {
+  XPG_REQ(M >= 0 && M <= (int64_t(1) << 40), "post: M out of range");
+  XPG_REQ(ld >= 4 && ld <= 256 && ld % 4 == 0, "post: ld must be a multiple of 4 in 4..256");
+  XPG_REQ(f_out >= 1 && f_out <= ld, "post: 1 <= f_out <= ld required");
+  return XPG_OK;
+}
+
+int launch_post(float* h, int64_t M, int64_t ld, int64_t f_out, const xpg_post_desc& q, const float* hprev,
+                int64_t ld_prev, int64_t n_tgt, int64_t n_prev, const int32_t* tgt_prev, hipStream_t st) {
+  if (const int rc = post_desc_check(q)) return rc;
+  if (const int rc = post_shape_check(M, ld, f_out)) return rc;
+  if (q.residual) {
+    XPG_REQ(hprev && tgt_prev, "post: residual needs hprev and tgt_prev");
+    XPG_REQ(ld_prev >= ld && ld_prev % 4 == 0, "post: residual needs ld_prev >= ld, a multiple of 4");
+    XPG_REQ(n_tgt >= 1 && n_tgt <= INT32_MAX && n_prev >= 1 && n_prev <= INT32_MAX && M % n_tgt == 0,
+            "post: residual needs M = rows * n_tgt and n_prev >= 1");
+    XPG_REQ(reinterpret_cast<uintptr_t>(hprev) % 16 == 0, "post: hprev must be 16-byte aligned");
+  }
+  if (M == 0) return XPG_OK;
+  XPG_REQ(h && reinterpret_cast<uintptr_t>(h) % 16 == 0, "post: h must be non-null and 16-byte aligned");
+  for (const float* v : {q.scale, q.shift, q.gamma, q.beta})
+    XPG_REQ(reinterpret_cast<uintptr_t>(v) % 16 == 0, "post: scale / shift / gamma / beta must be 16-byte aligned");
+  PostArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.h = h;
+  a.M = M;
+  a.ld = static_cast<int>(ld);
+  a.f_out = static_cast<int>(f_out);
+  a.group = post_group(ld);
+  a.eps = q.eps;
+  a.scale = q.scale;
+  a.shift = q.shift;
+  a.gamma = q.gamma;
+  a.beta = q.beta;
+  a.act = q.act;
+  if (q.residual) {
+    a.hprev = hprev;
+    a.ld_prev = static_cast<int>(ld_prev);
+    a.n_tgt = static_cast<int>(n_tgt);
+    a.n_prev = static_cast<int>(n_prev);
+    a.tgt_prev = tgt_prev;
+  }
+  const int64_t per_block = (int64_t)kPostWaves * (64 / a.group);
+  const dim3 grid(static_cast<unsigned>(std::min<int64_t>(cdiv(M, per_block), 1 << 20))), block(64 * kPostWaves);
+  if (q.norm == XPG_NORM_LAYER) {
+    if (q.residual) hipLaunchKernelGGL((k_post<XPG_NORM_LAYER, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_post<XPG_NORM_LAYER, false>), grid, block, 0, st, a);
+  } else {
+    if (q.residual) hipLaunchKernelGGL((k_post<XPG_NORM_NONE, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_post<XPG_NORM_NONE, false>), grid, block, 0, st, a);
+  }
+  XPG_LAUNCHED();
+  return XPG_OK;
+}
+
 // ------------------------------------------------------------------------------------ helpers
 size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
+
+// plans with a post-op on any layer run on the multi-kernel path only
+bool plan_has_post(const xpg_forward_plan* p, const xpg_post_desc* post) {
+  if (!post || !p || !p->layers) return false;
+  for (int l = 0; l < p->n_layers; ++l)
+    if (post_any(post[l])) return true;
+  return false;
+}
+// the host checks of a plan's post records (xpgnn.h, xpg_post_desc): before any launch
+int post_plan_check(const xpg_forward_plan* p, const xpg_post_desc* post) {
+  if (!plan_has_post(p, post)) return XPG_OK;
+  XPG_REQ(!p->edge_masks, "masked_forward: post-ops do not take edge-mask plans (edge_masks)");
+  XPG_REQ(!p->edge_dot, "masked_forward: post-ops do not take a link decoder (edge_dot)");
+  for (int l = 0; l < p->n_layers; ++l)
+    XPG_REQ(p->layers[l].tgt_type == nullptr && p->layers[l].n_types <= 1,
+            "masked_forward: post-ops do not take multi-node-type plans (n_types > 1)");
+  for (int l = 0; l < p->n_layers; ++l) {
+    const xpg_post_desc& q = post[l];
+    if (!post_any(q)) continue;
+    const xpg_layer_desc& ly = p->layers[l];
+    if (const int rc = post_desc_check(q)) return rc;
+    XPG_REQ(ly.act == XPG_ACT_NONE, "masked_forward: a layer with a post-op must have act NONE (the post-op applies it)");
+    XPG_REQ(ly.f_out >= 1 && ly.f_out <= ly.f_out_pad && ly.f_out_pad % 4 == 0 && ly.f_out_pad <= 256,
+            "masked_forward: post-op layer widths");
+    if (q.residual) {
+      XPG_REQ(l > 0, "masked_forward: residual on layer 1 (there is no previous layer's row)");
+      XPG_REQ(ly.f_out_pad == p->layers[l - 1].f_out_pad,
+              "masked_forward: residual needs f_out_pad equal to the previous layer's");
+      XPG_REQ(ly.tgt_prev != nullptr, "masked_forward: residual needs tgt_prev");
+    }
+  }
+  return XPG_OK;
+}
 
 // pooled plans (xpg_layer_desc.pool on the last conv layer) run on the multi-kernel path only
 int plan_pool(const xpg_forward_plan* p) { return p->layers[p->n_layers - 1].pool; }
@@ -7677,8 +7870,9 @@ struct FwdLaunch {
   hipStream_t st;
   int* ctl;
 };
-int forward_route(const xpg_forward_plan* p, int64_t rows, WideWs* W, FwdPath* path, const FwdLaunch* go = nullptr) {
-  if (wide_wanted(p) && wide_layout(p, rows, W) == 0) {
+int forward_route(const xpg_forward_plan* p, int64_t rows, WideWs* W, FwdPath* path, const FwdLaunch* go = nullptr,
+                  bool post = false) {
+  if (!post && wide_wanted(p) && wide_layout(p, rows, W) == 0) {
     *path = kPathWide;
     return XPG_OK;
   }
@@ -7688,6 +7882,10 @@ int forward_route(const xpg_forward_plan* p, int64_t rows, WideWs* W, FwdPath* p
   const bool multi = forward_is("unfused");
   const bool strict = forward_is(nullptr) && !multi && strict_env && std::strcmp(strict_env, "1") == 0;
   *path = kPathNone;
+  if (post) {  // post-ops (xpg_post_desc): the multi-kernel path only
+    if (!strict) *path = kPathUnfused;
+    return XPG_OK;
+  }
   if (strict && forward_is("wide")) return XPG_OK;
   if (forward_is("fused")) {
     const int rc = go ? try_fused_forward(p, go->bits, rows, go->y, go->st)
@@ -8117,11 +8315,19 @@ int xpg_profile_read(double* ms, int64_t* launches, int32_t n_slots) {
 }
 
 int xpg_forward_workspace(const xpg_forward_plan* plan, int64_t rows, size_t* bytes) {
+  return xpg_forward_workspace_post(plan, nullptr, rows, bytes);
+}
+
+// The post-ops work in place on the layers' output rows: the layout is that of the same plan
+// without them, on the multi-kernel path.
+int xpg_forward_workspace_post(const xpg_forward_plan* plan, const xpg_post_desc* post, int64_t rows, size_t* bytes) {
   WsLayout L;
   int rc = layout_ws(plan, rows, &L);
   if (rc) return rc;
+  rc = post_plan_check(plan, post);
+  if (rc) return rc;
   WideWs W;
-  if (wide_wanted(plan) && wide_layout(plan, rows, &W) == 0) {
+  if (!plan_has_post(plan, post) && wide_wanted(plan) && wide_layout(plan, rows, &W) == 0) {
     *bytes = W.total;  // 32-row passes: one buffer set, or two when rows > 32
     return XPG_OK;
   }
@@ -8130,15 +8336,23 @@ int xpg_forward_workspace(const xpg_forward_plan* plan, int64_t rows, size_t* by
 }
 
 int xpg_forward_describe(const xpg_forward_plan* p, int64_t rows, char* buf, size_t n) {
+  return xpg_forward_describe_post(p, nullptr, rows, buf, n);
+}
+
+int xpg_forward_describe_post(const xpg_forward_plan* p, const xpg_post_desc* post, int64_t rows, char* buf,
+                              size_t n) {
   XPG_REQ(buf != nullptr && n > 0, "forward_describe: no buffer");
   buf[0] = 0;
   WsLayout L;
   int rc = layout_ws(p, rows, &L);
   if (rc) return rc;
   XPG_REQ(p->n_rel >= 1 && p->n0 >= 1 && p->cols > 0, "masked_forward: bad plan sizes");
+  rc = post_plan_check(p, post);
+  if (rc) return rc;
+  const bool has_post = plan_has_post(p, post);
   WideWs W;
   FwdPath path;
-  rc = forward_route(p, rows, &W, &path);
+  rc = forward_route(p, rows, &W, &path, nullptr, has_post);
   if (rc) return rc;
   if (path == kPathNone) return fail(XPG_EINVAL, kStrictMsg);
   std::string s = kPathName[path];
@@ -8148,6 +8362,9 @@ int xpg_forward_describe(const xpg_forward_plan* p, int64_t rows, char* buf, siz
     if (rc) return rc;
     s += std::string(" l1=") + pick.k1->name + " l2=" + pick.k2->name;
   }
+  if (has_post)  // each post layer's kernel, by layer number (1-based, as l1 / l2 above)
+    for (int l = 0; l < p->n_layers; ++l)
+      if (post_any(post[l])) s += " post" + std::to_string(l + 1) + "=" + post_kernel_name(post[l]);
   if (s.size() + 1 > n) return fail(XPG_ENOSPC, "forward_describe: buffer too small");
   std::memcpy(buf, s.c_str(), s.size() + 1);
   return XPG_OK;
@@ -8189,12 +8406,40 @@ int xpg_pool_describe(int64_t rows, int64_t n, int64_t ld, int32_t kind, char* b
   return XPG_OK;
 }
 
+int xpg_post_rows(float* h, int64_t M, int64_t ld, int64_t f_out, const xpg_post_desc* post, const float* hprev,
+                  int64_t ld_prev, int64_t n_tgt, int64_t n_prev, const int32_t* tgt_prev, xpg_stream_t stream) {
+  XPG_REQ(post != nullptr, "post_rows: no record");
+  return launch_post(h, M, ld, f_out, *post, hprev, ld_prev, n_tgt, n_prev, tgt_prev, S(stream));
+}
+
+int xpg_post_describe(int64_t M, int64_t ld, int64_t f_out, const xpg_post_desc* post, char* buf, size_t nbytes) {
+  XPG_REQ(buf != nullptr && nbytes > 0, "post_describe: no buffer");
+  buf[0] = 0;
+  XPG_REQ(post != nullptr, "post_describe: no record");
+  if (const int rc = post_desc_check(*post)) return rc;
+  if (const int rc = post_shape_check(M, ld, f_out)) return rc;
+  const int g = post_group(ld);
+  const std::string s = std::string(post_kernel_name(*post)) + " group=" + std::to_string(g) +
+                        " rows_per_wave=" + std::to_string(64 / g);
+  if (s.size() + 1 > nbytes) return fail(XPG_ENOSPC, "post_describe: buffer too small");
+  std::memcpy(buf, s.c_str(), s.size() + 1);
+  return XPG_OK;
+}
+
 int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t rows, float* y,
                        void* workspace, size_t workspace_bytes, xpg_stream_t stream) {
+  return xpg_masked_forward_post(p, nullptr, bits, rows, y, workspace, workspace_bytes, stream);
+}
+
+int xpg_masked_forward_post(const xpg_forward_plan* p, const xpg_post_desc* post, const uint32_t* bits, int64_t rows,
+                            float* y, void* workspace, size_t workspace_bytes, xpg_stream_t stream) {
   WsLayout L;
   int rc = layout_ws(p, rows, &L);
   if (rc) return rc;
   XPG_REQ(p->n_rel >= 1 && p->n0 >= 1 && p->cols > 0, "masked_forward: bad plan sizes");
+  rc = post_plan_check(p, post);
+  if (rc) return rc;
+  const bool has_post = plan_has_post(p, post);
   XPG_REQ(!p->edge_masks || !(plan_has_kind(p, XPG_TERM_SUM) || plan_has_kind(p, XPG_TERM_MAX)),
           "masked_forward: SUM / MAX terms do not take edge-mask plans");
   rc = rel_plan_check(p);
@@ -8206,7 +8451,7 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
   // hold (a wide plan returns before `go` is read; its workspace is checked below)
   const bool ready = workspace_bytes >= L.total && rows != 0;
   const FwdLaunch go{bits, y, st, workspace ? reinterpret_cast<int*>(static_cast<char*>(workspace) + L.ctl) : nullptr};
-  rc = forward_route(p, rows, &W, &path, ready ? &go : nullptr);
+  rc = forward_route(p, rows, &W, &path, ready ? &go : nullptr, has_post);
   if (rc) return rc;
   if (path == kPathWide) {
     XPG_REQ(workspace_bytes >= W.total, "masked_forward: workspace too small");
@@ -8231,7 +8476,11 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
   // Nor does an ATT2 last layer end in a dense launch (k_agg_att2 finishes the layer itself).
   const int pool = plan_pool(p);
   const bool last_att2 = layer_has_att2(p->layers[p->n_layers - 1]);
-  if (!p->edge_dot && p->n_head >= 1 && (p->n_head >= 2 || (p->n_layers >= 2 && !pool && !last_att2))) {
+  // Nor may a last conv layer with a post-op take the column pick or the first head layer into its
+  // k_dense epilogue: the post-op runs between the two.
+  const bool last_post = has_post && post_any(post[p->n_layers - 1]);
+  if (!p->edge_dot && p->n_head >= 1 &&
+      (p->n_head >= 2 || (p->n_layers >= 2 && !pool && !last_att2 && !last_post))) {
     const xpg_head_desc& hl = p->head[p->n_head - 1];
     const int64_t prev_pad = p->n_head >= 2 ? p->head[p->n_head - 2].n_pad : p->layers[p->n_layers - 1].f_out_pad;
     if (hl.k_pad == prev_pad && p->out_col >= 0 && p->out_col < hl.n_real) {
@@ -8249,7 +8498,8 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
                        kpitch, p->n_rel, p->f0_node, p->deg_ptr, p->deg_src, p->edge_masks ? p->deg_eid : nullptr, kin);
     XPG_LAUNCHED();
   }
-  for (int l = 0; l < p->n_layers; ++l) {
+  // one conv layer: its rows into ws + L.h[l] (XPG_REQ and the launchers return from the lambda)
+  auto run_layer = [&](int l) -> int {
     const xpg_layer_desc& ly = p->layers[l];
     XPG_REQ(ly.n_terms >= 1 && ly.n_terms <= XPG_MAX_TERMS, "layer: 1..8 terms");
     const bool raw = l == 0 && plan_raw_l1(p);
@@ -8257,7 +8507,7 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
       rc = launch_att2_layer(p, l, bits, rows, l == 0 ? nullptr : reinterpret_cast<const float*>(ws + L.h[l - 1]),
                              reinterpret_cast<float*>(ws + L.xlr), reinterpret_cast<float*>(ws + L.h[l]), st);
       if (rc) return rc;
-      continue;
+      return XPG_OK;
     }
     if (layer_has_attention(ly)) {
       XPG_REQ(!raw, "layer 1: attention terms do not take the raw form");
@@ -8265,7 +8515,7 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
       if (l == 0) {
         rc = launch_att_layer(p, l, bits, rows, nullptr, nullptr, hout, st);
         if (rc) return rc;
-        continue;
+        return XPG_OK;
       }
       const xpg_layer_desc& prev = p->layers[l - 1];
       XPG_REQ(ly.f_in_pad == prev.f_out_pad && ly.weight, "layer: f_in_pad must equal previous f_out_pad");
@@ -8278,14 +8528,14 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
       rc = launch_dense(agg, rows * ly.n_tgt, K, ly.weight, K, K, ly.bias, ly.f_out, ly.f_out_pad, ly.act, hout,
                         ly.f_out_pad, st, ly.tgt_type, ly.n_tgt, ly.f_out_pad, fuse_here ? &fh : nullptr);
       if (rc) return rc;
-      continue;
+      return XPG_OK;
     }
     if (layer_has_rel(ly)) {
       float* hout = reinterpret_cast<float*>(ws + L.h[l]);
       if (l == 0) {
         rc = launch_rel_layer(p, l, bits, rows, nullptr, hout, st);
         if (rc) return rc;
-        continue;
+        return XPG_OK;
       }
       const xpg_layer_desc& prev = p->layers[l - 1];
       XPG_REQ(ly.f_in_pad == prev.f_out_pad, "layer: f_in_pad must equal previous f_out_pad");
@@ -8297,7 +8547,7 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
       rc = launch_dense(agg, rows * ly.n_tgt, K, ly.weight, K, K, ly.bias, ly.f_out, ly.f_out_pad, ly.act, hout,
                         ly.f_out_pad, st, ly.tgt_type, ly.n_tgt, ly.f_out_pad, fuse_here ? &fh : nullptr);
       if (rc) return rc;
-      continue;
+      return XPG_OK;
     }
     AggArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -8384,6 +8634,20 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
       rc = launch_dense(agg, rows * ly.n_tgt, a.out_ld, ly.weight, a.out_ld, a.out_ld, ly.bias, ly.f_out,
                         ly.f_out_pad, ly.act, hout, ly.f_out_pad, st, ly.tgt_type, ly.n_tgt, ly.f_out_pad,
                         fuse_here ? &fh : nullptr);
+      if (rc) return rc;
+    }
+    return XPG_OK;
+  };
+  for (int l = 0; l < p->n_layers; ++l) {
+    rc = run_layer(l);
+    if (rc) return rc;
+    if (has_post && post_any(post[l])) {  // in place on the layer's rows, before the readout / the head
+      const xpg_layer_desc& ly = p->layers[l];
+      const bool res = post[l].residual != 0;  // post_plan_check: l > 0, equal padded widths, tgt_prev
+      rc = launch_post(reinterpret_cast<float*>(ws + L.h[l]), rows * ly.n_tgt, ly.f_out_pad, ly.f_out, post[l],
+                       res ? reinterpret_cast<const float*>(ws + L.h[l - 1]) : nullptr,
+                       res ? p->layers[l - 1].f_out_pad : 0, ly.n_tgt, res ? p->layers[l - 1].n_tgt : 0, ly.tgt_prev,
+                       st);
       if (rc) return rc;
     }
   }

@@ -552,6 +552,60 @@ def pool_rows(h: torch.Tensor, kind: str, out: torch.Tensor = None,
     return out
 
 
+# ----------------------------------------------------------------------------- post-op
+def _post_record(ld, norm, eps, act, residual, vecs, device, keep):
+    pd = _lib.PostDesc(norm=_lib.NORM[norm], eps=float(eps), act=ACT[act], residual=int(bool(residual)))
+    for name, v in vecs.items():
+        if v is None:
+            continue
+        vp = _pad_vec(torch.as_tensor(v).reshape(-1), ld, device)
+        keep.append(vp)
+        setattr(pd, name, vp.data_ptr())
+    return pd
+
+
+def post_describe(M: int, ld: int, f_out: int, norm=None, residual=False) -> str:
+    """The kernel post_rows launches for h [M, ld] (xpg_post_describe, a host query sharing the
+    launcher's selection): `k_post<NORM,RES> group=G rows_per_wave=R`."""
+    pd = _lib.PostDesc(norm=_lib.NORM[norm], eps=1.0, residual=int(bool(residual)))
+    buf = ctypes.create_string_buffer(128)
+    _lib.check(_lib.load().xpg_post_describe(int(M), int(ld), int(f_out), ctypes.byref(pd), buf, len(buf)))
+    return buf.value.decode()
+
+
+def post_rows(h: torch.Tensor, f_out: int, scale=None, shift=None, norm=None, gamma=None, beta=None,
+              eps=1e-5, act=None, hprev: torch.Tensor = None, tgt_prev: torch.Tensor = None):
+    """One conv layer's post-op in place on h [M, ld] fp32 (xpg_post_rows; k_post on its own):
+    h * scale + shift, norm "layer" over the first f_out columns with gamma / beta / eps, act, and
+    with `hprev` [rows, n_prev, ld_prev] and `tgt_prev` int32 [n_tgt] (M = rows * n_tgt) the skip
+    + hprev[r, tgt_prev[t]]; columns f_out.. come out 0.  The vectors hold f_out entries (or None).
+    Returns h."""
+    _lib.require_device(h, "h")
+    if h.dtype != torch.float32 or h.dim() != 2 or not h.is_contiguous():
+        raise ValueError("h must be a contiguous float32 [M, ld] tensor")
+    M, ld = h.shape
+    res = hprev is not None
+    if res:
+        if hprev.dtype != torch.float32 or hprev.dim() != 3 or not hprev.is_contiguous() or \
+                tgt_prev is None or tgt_prev.dtype != torch.int32 or hprev.device != h.device or \
+                tgt_prev.device != h.device:
+            raise ValueError("hprev must be a contiguous float32 [rows, n_prev, ld_prev] tensor and "
+                             "tgt_prev an int32 tensor, both on h's device")
+        rows, n_prev, ld_prev = hprev.shape
+        n_tgt = tgt_prev.numel()
+        if n_tgt == 0 or M != rows * n_tgt or \
+                (n_tgt and (int(tgt_prev.min()) < 0 or int(tgt_prev.max()) >= n_prev)):
+            raise ValueError("M must be rows * len(tgt_prev) and tgt_prev must index hprev's rows")
+    else:
+        n_prev = ld_prev = n_tgt = 0
+    keep = []
+    pd = _post_record(ld, norm, eps, act, res, {"scale": scale, "shift": shift, "gamma": gamma,
+                                                "beta": beta}, h.device, keep)
+    call("xpg_post_rows", ptr(h), M, ld, int(f_out), ctypes.byref(pd), ptr(hprev), ld_prev, n_tgt,
+         n_prev, ptr(tgt_prev), _lib.stream_of(h.device))
+    return h
+
+
 # ----------------------------------------------------------------------------- forward plan
 def plan_arrays(S, rel_np, queries, L, rel_eid=None):
     """Receptive-field frontiers and CSR arrays of a ForwardPlan, built on the host by the
@@ -1083,6 +1137,32 @@ class ForwardPlan:
             prev_pad = f_out_pad
         if self.pool is not None:
             self._layers[L - 1].pool = _lib.POOL[self.pool]
+        # post-ops (xpgnn.h, xpg_post_desc): one host record per conv layer, all zero = none; their
+        # vectors are the program's, zero-padded to the layer's width
+        self._post = None
+        if any(getattr(c, "post", None) is not None for c in program.convs):
+            if self.edge_masks or link is not None:
+                raise ValueError("post-ops (LayerNorm, residual, BatchNorm after attention) on "
+                                 "edge-mask plans are not supported")
+            if program.n_types > 1:
+                raise ValueError("post-ops on multi-node-type programs are not supported")
+            self._post = (_lib.PostDesc * L)()
+            for li, conv in enumerate(program.convs):
+                q = conv.post
+                if q is None:
+                    continue
+                pd = self._post[li]
+                pd.norm, pd.eps = _lib.NORM[q.norm], float(q.eps)
+                pd.act, pd.residual = ACT[q.act], int(bool(q.residual))
+                for name in ("scale", "shift", "gamma", "beta"):
+                    v = getattr(q, name)
+                    if v is None:
+                        continue
+                    vp = self._program_tensor(
+                        program, ("post", li, name),
+                        lambda v=v, n=self._layers[li].f_out_pad: _pad_vec(v.reshape(-1), n, device))
+                    self._keep.append(vp)
+                    setattr(pd, name, vp.data_ptr())
 
         self._head = (HeadDesc * max(1, len(program.head)))()
         for i, h in enumerate(program.head):
@@ -1177,18 +1257,28 @@ class ForwardPlan:
         held = self._keep + ([self._ws] if self._ws is not None else [])
         return sum(t.numel() * t.element_size() for t in held)
 
+    def _entry(self, name):
+        """The entry point and its leading arguments: `name`(plan, ...), or with post-ops
+        `name`_post(plan, post records, ...)."""
+        if self._post is None:
+            return name, (ctypes.byref(self.desc),)
+        return name + "_post", (ctypes.byref(self.desc), self._post)
+
     def workspace_bytes(self, rows):
         n = ctypes.c_size_t(0)
-        _lib.check(_lib.load().xpg_forward_workspace(ctypes.byref(self.desc), rows, ctypes.byref(n)))
+        name, lead = self._entry("xpg_forward_workspace")
+        _lib.check(getattr(_lib.load(), name)(*lead, rows, ctypes.byref(n)))
         return n.value
 
     def describe(self, rows):
         """The path forward() takes for `rows` mask rows under the current environment: "rows",
         "fused", "unfused", or "wide l1=<kernel> l2=<kernel>" with the kernels' template
-        arguments.  A host query of the library's own dispatch (nothing is launched); raises
+        arguments; a plan with post-ops: "unfused post<l>=k_post<NORM,RES> ..." (each post layer's
+        kernel).  A host query of the library's own dispatch (nothing is launched); raises
         where forward() would refuse the plan (XPG_FORWARD_STRICT=1)."""
-        buf = ctypes.create_string_buffer(256)
-        _lib.check(_lib.load().xpg_forward_describe(ctypes.byref(self.desc), rows, buf, len(buf)))
+        buf = ctypes.create_string_buffer(1024)
+        name, lead = self._entry("xpg_forward_describe")
+        _lib.check(getattr(_lib.load(), name)(*lead, rows, buf, len(buf)))
         return buf.value.decode()
 
     def forward(self, bits: torch.Tensor, max_ws_bytes=8 << 30, out: torch.Tensor = None,
@@ -1213,12 +1303,12 @@ class ForwardPlan:
         if rows == 0:
             return y
         st = _lib.stream_of(self.device)
+        fwd, lead = self._entry("xpg_masked_forward")
         if workspace is not None:
             if workspace.dtype != torch.uint8 or workspace.device != self.device or \
                     workspace.numel() < self.workspace_bytes(rows):
                 raise ValueError("workspace must be a uint8 device tensor of workspace_bytes(rows)")
-            call("xpg_masked_forward", ctypes.byref(self.desc), ptr(bits), rows, ptr(y),
-                 ptr(workspace), workspace.numel(), st)
+            call(fwd, *lead, ptr(bits), rows, ptr(y), ptr(workspace), workspace.numel(), st)
             return y
         w1, w2 = self.workspace_bytes(1), self.workspace_bytes(2)
         per_row = max(0, w2 - w1)  # 0: a rows-independent workspace (the wide 32-row passes)
@@ -1239,8 +1329,8 @@ class ForwardPlan:
         self._ws_stream = cur
         for r0 in range(0, rows, chunk):
             n = min(chunk, rows - r0)
-            call("xpg_masked_forward", ctypes.byref(self.desc), ptr(bits[r0:r0 + n]), n,
-                 ptr(y[r0:r0 + n]), ptr(self._ws), self._ws.numel(), st)
+            call(fwd, *lead, ptr(bits[r0:r0 + n]), n, ptr(y[r0:r0 + n]), ptr(self._ws),
+                 self._ws.numel(), st)
         return y
 
 

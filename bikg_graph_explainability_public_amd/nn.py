@@ -7,7 +7,9 @@ PyTorch Geometric is not available on ROCm boxes here; these modules carry the s
 GINConv, `weight` / `comp` / `root` / `bias` for RGCNConv, `convs.<src>__<rel>__<dst>.*` for
 HeteroConv, `weight` / `bias` for Linear) so the reference checkpoints (test_data/*.pth.tar, tests/test_utils.py:10-83) load
 unchanged.  Their torch `forward` is the semantics the HIP engine compiles (engine.py); the
-engine recognises these classes and the real PyG classes by name and attributes.
+engine recognises these classes and the real PyG classes by name and attributes.  The model
+families built from them (ConvStack, BlockStack with norm layers and skips, RGCNStack, the hetero
+stacks, LinkModel / RelLinkModel, PooledModel) follow the registration order the lowering walks.
 """
 import math
 
@@ -517,6 +519,91 @@ class ConvStack(nn.Module):
                 x = c(x)
         if isinstance(x, dict):
             x = x[list(x.keys())[0]]
+        for layer in self.fc:
+            x = layer(x)
+        return x
+
+
+class BlockStack(nn.Module):
+    """Normalised / residual model family on a homogeneous graph: `conv` = ModuleList[Conv, norm?,
+    ReLU]*, `fc` = ModuleList[Linear, act]* as in ConvStack (fc_dims of at most one width: no head,
+    e.g. as a PooledModel encoder).  Block i: z = conv_i(h, edge_index); z = norm_i(z); z = relu(z);
+    h = z + h with `residual` where z and h have the same width (a block that changes the width,
+    normally block 0, takes no skip), else h = z.
+
+    `kind`: every ConvStack kind.  `norm`: None, "batch" (torch.nn.BatchNorm1d(width)) or "layer"
+    (torch.nn.LayerNorm(width)); `width` = dims[i + 1] * heads[i] for "gat" / "gatv2".  kind "gin"
+    with norm "batch" is the textbook GIN block GINConv(Sequential(Linear, BatchNorm1d, ReLU,
+    Linear)) with no norm after the conv; with norm "layer" the LayerNorm follows the conv.
+
+    The engine lowers this family by class name plus the `residual` attribute (program.compile_arch):
+    BatchNorm in eval mode folds into the weights (a post-op affine after attention layers),
+    LayerNorm and the skip are the layer's post-op (k_post in csrc/xpgnn.hip)."""
+
+    def __init__(self, kind, dims, fc_dims, norm=None, residual=False, final_act="sigmoid", heads=None,
+                 add_self_loops=True, share_weights=False):
+        super().__init__()
+        if norm not in (None, "batch", "layer"):
+            raise ValueError("BlockStack norm must be None, 'batch' or 'layer'")
+        n_conv = len(dims) - 1
+        attn = kind in ("gat", "gatv2")
+        if attn:
+            heads = [1] * n_conv if heads is None else [int(h) for h in heads]
+            if len(heads) != n_conv:
+                raise ValueError("heads must give one entry per conv layer")
+        elif heads is not None:
+            raise ValueError("heads applies to kind='gat' / 'gatv2' only")
+        if share_weights and kind != "gatv2":
+            raise ValueError("share_weights applies to kind='gatv2' only")
+        self.kind, self.norm, self.residual = kind, norm, bool(residual)
+
+        def gin(i, o):
+            mlp = [Linear(i, o)] + ([nn.BatchNorm1d(o)] if norm == "batch" else []) + \
+                [nn.ReLU(), Linear(o, o)]
+            return GINConv(nn.Sequential(*mlp))
+        makers = {
+            "gcn": GCNConv, "sage": SAGEConv,
+            "sage-add": lambda i, o: SAGEConv(i, o, aggr="add"),
+            "sage-max": lambda i, o: SAGEConv(i, o, aggr="max"),
+            "graphconv": GraphConv,
+            "graphconv-max": lambda i, o: GraphConv(i, o, aggr="max"),
+            "gin": gin,
+        }
+        if not attn and kind not in makers:
+            raise ValueError(f"unknown BlockStack kind {kind!r}")
+        convs = []
+        self.block_len = 2 + (norm is not None and not (kind == "gin" and norm == "batch"))
+        for i in range(n_conv):
+            f_in, f_out = dims[i], dims[i + 1]
+            if attn:
+                f_in, width = f_in * (heads[i - 1] if i else 1), f_out * heads[i]
+                if kind == "gatv2":
+                    convs.append(GATv2Conv(f_in, f_out, heads=heads[i], add_self_loops=add_self_loops,
+                                           share_weights=share_weights))
+                else:
+                    convs.append(GATConv(f_in, f_out, heads=heads[i], add_self_loops=add_self_loops))
+            else:
+                width = f_out
+                convs.append(makers[kind](f_in, f_out))
+            if self.block_len == 3:
+                convs.append(nn.BatchNorm1d(width) if norm == "batch" else nn.LayerNorm(width))
+            convs.append(nn.ReLU())
+        self.conv = nn.ModuleList(convs)
+        fcs = []
+        for i in range(len(fc_dims) - 1):
+            fcs.append(Linear(fc_dims[i], fc_dims[i + 1]))
+            last = i == len(fc_dims) - 2
+            fcs.append((nn.Sigmoid() if final_act == "sigmoid" else nn.Identity()) if last
+                       else nn.ReLU())
+        self.fc = nn.ModuleList(fcs)
+
+    def forward(self, x, edge_index):
+        n = self.block_len
+        for i in range(0, len(self.conv), n):
+            z = self.conv[i](x, edge_index)
+            for m in self.conv[i + 1:i + n]:
+                z = m(z)
+            x = z + x if self.residual and z.shape[-1] == x.shape[-1] else z
         for layer in self.fc:
             x = layer(x)
         return x

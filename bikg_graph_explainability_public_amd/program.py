@@ -10,6 +10,12 @@ layout of tests/test_utils.py:10-83 and the notebooks) — and lowers it to:
     ConvLayer(terms=[(kind, relation, W_k)], bias_sum, act)   per conv layer
     HeadLayer(W, b, act)                                       per Linear
 
+Blocks `[conv norm? act?]+ [Linear norm? act?]*`: a BatchNorm1d in eval mode folds into the linear
+map before it where that map is the last thing the layer does (every term kind but attention, the
+first Linear of a GINConv MLP, a head Linear); after an attention layer it becomes the layer's
+post-op affine, a torch.nn.LayerNorm after a conv the post-op's norm (ConvLayer.post, PostOp).
+nn.BlockStack(residual=True), matched by class name, adds the skip to the post-op.
+
 Multi-node-type graphs (HeteroConv over relations (src, rel, dst) between several node types,
 model.py:118-253): every term carries its relation's destination type (the engine applies it
 only to targets of that type), SAGE root weights and biases are summed per destination type,
@@ -64,12 +70,28 @@ class Term:
 
 
 @dataclass
+class PostOp:
+    """What follows a conv layer's bias, row by row (xpgnn.h, xpg_post_desc), in this order:
+    v * scale + shift, the norm (v - mean) / sqrt(var + eps) * gamma + beta over the f_out columns,
+    act, + the target's own input row (residual).  fp32 [f_out] tensors; None = 1 / 0 / no norm."""
+    scale: Optional[torch.Tensor] = None
+    shift: Optional[torch.Tensor] = None
+    norm: Optional[str] = None          # None | "layer"
+    gamma: Optional[torch.Tensor] = None
+    beta: Optional[torch.Tensor] = None
+    eps: float = 0.0
+    act: Optional[str] = None
+    residual: bool = False
+
+
+@dataclass
 class ConvLayer:
     terms: List[Term]
     bias: torch.Tensor    # [f_out] (sum over relations); multi-node-type: [n_types, f_out]
-    act: Optional[str]
+    act: Optional[str]    # None when `post` is set: the activation is the post-op's
     f_in: int
     f_out: int
+    post: Optional[PostOp] = None
 
 
 @dataclass
@@ -100,6 +122,10 @@ class ModelProgram:
     @property
     def hops(self):
         return len(self.convs) - self.extra_layers
+
+    @property
+    def has_post(self):
+        return any(c.post is not None for c in self.convs)
 
 
 _ACTS = {"ReLU": "relu", "Sigmoid": "sigmoid", "Tanh": "tanh", "ELU": "elu",
@@ -152,12 +178,93 @@ def _is_linear(m):
     return type(m).__name__ == "Linear" and hasattr(m, "weight")
 
 
+def _is_bn(m):
+    return type(m).__name__ == "BatchNorm1d" and hasattr(m, "running_mean") and hasattr(m, "eps")
+
+
+def _is_ln(m):
+    return type(m).__name__ == "LayerNorm"
+
+
+def _is_norm(m):
+    return _is_bn(m) or _is_ln(m)
+
+
+def _bn_affine(bn, width):
+    """BatchNorm1d in eval mode as the per-column affine v * s + t, s = gamma / sqrt(var + eps),
+    t = beta - mean * s (fp64).  Training mode or no running statistics: its statistics would be
+    those of the whole B-fold union graph."""
+    if bn.training:
+        raise UnsupportedArch("BatchNorm1d in training mode (batch statistics over the union graph)")
+    if not getattr(bn, "track_running_stats", True) or bn.running_mean is None or bn.running_var is None:
+        raise UnsupportedArch("BatchNorm1d without running statistics")
+    if int(bn.num_features) != int(width):
+        raise UnsupportedArch(f"BatchNorm1d({bn.num_features}) after a layer of width {width}")
+    s = (bn.running_var.detach().double() + float(bn.eps)).rsqrt()
+    if getattr(bn, "weight", None) is not None:
+        s = s * bn.weight.detach().double()
+    t = -bn.running_mean.detach().double() * s
+    if getattr(bn, "bias", None) is not None:
+        t = t + bn.bias.detach().double()
+    return s, t
+
+
+def _fold_rows(w, s):
+    """diag(s) w, in fp64 and rounded once; the leading dimensions of `w` are kept."""
+    return (s.reshape(-1, 1) * w.detach().double()).to(torch.float32)
+
+
+def _fold_bias(b, s, t, width):
+    b = torch.zeros(width, dtype=torch.float64) if b is None else b.detach().double()
+    return (s * b + t).to(torch.float32)
+
+
+def _layer_norm_post(ln, width):
+    if not isinstance(ln, nn.LayerNorm):
+        raise UnsupportedArch(f"a LayerNorm that is not torch.nn.LayerNorm ({type(ln).__module__})")
+    shape = tuple(ln.normalized_shape)
+    if len(shape) != 1 or int(shape[0]) != int(width):
+        raise UnsupportedArch(f"LayerNorm{shape} after a layer of width {width} (last dimension only)")
+    return PostOp(norm="layer", eps=float(ln.eps),
+                  gamma=_f32(ln.weight) if getattr(ln, "weight", None) is not None else None,
+                  beta=_f32(ln.bias) if getattr(ln, "bias", None) is not None else None)
+
+
+_FOLD_KINDS = ("gcn", "mean", "sum", "max", "root")
+
+
+def _norm_conv_layer(layer, norm):
+    """Apply the norm module that follows conv layer `layer` (before its activation): fold, or a
+    post-op that takes the activation with it."""
+    kinds = {t.kind for t in layer.terms}
+    if "rel" in kinds:
+        raise UnsupportedArch(f"{type(norm).__name__} after RGCNConv")
+    if layer.bias.dim() != 1:
+        raise UnsupportedArch(f"{type(norm).__name__} on a multi-node-type graph")
+    if _is_bn(norm):
+        s, t = _bn_affine(norm, layer.f_out)
+        if kinds <= set(_FOLD_KINDS):
+            # the layer ends in its linear maps: sum_k (diag(s) W_k) agg_k + (s b + t); the
+            # aggregations (max included) come before them, so the sign of s does not matter
+            for term in layer.terms:
+                term.weight = _fold_rows(term.weight, s)
+            layer.bias = _fold_bias(layer.bias, s, t, layer.f_out)
+            return
+        # attention: the scores read the transformed rows, which must stay as they are
+        layer.post = PostOp(scale=s.to(torch.float32), shift=t.to(torch.float32), act=layer.act)
+    else:
+        layer.post = _layer_norm_post(norm, layer.f_out)
+        layer.post.act = layer.act
+    layer.act = None
+
+
 def _leaf_units(module, attention=False):
-    """Registration-order walk yielding conv / linear / activation units (convs not entered)."""
+    """Registration-order walk yielding conv / linear / norm / activation units (convs not entered)."""
     for child in module.children():
         if _is_gatv2(child) and not attention:
             raise UnsupportedArch("GATv2Conv without the attention opt-in (attention=True)")
-        if _is_conv(child, attention) or _is_linear(child) or _act_name(child) is not None:
+        if _is_conv(child, attention) or _is_linear(child) or _act_name(child) is not None \
+                or _is_norm(child):
             yield child
         elif type(child).__name__ in _SKIP:
             continue
@@ -302,26 +409,35 @@ def _gin_terms(conv, rel):
     """GINConv: nn((1 + eps) x + sum_j x_j).  nn = Linear(W, b): a "sum" term W, the root
     (1 + eps) W and bias b.  nn = Sequential(Linear, act, Linear[, act]): that layer with the
     inner activation, then (returned as `extra`) the second Linear and the trailing activation
-    (None: the one that follows the conv) for a ROOT-only layer."""
+    (None: the one that follows the conv) for a ROOT-only layer.  A BatchNorm1d (eval mode)
+    between the first Linear and the inner activation folds into that Linear."""
     eps = conv.eps
     eps = float(eps.detach().reshape(-1)[0]) if isinstance(eps, torch.Tensor) else float(eps)
     mlp = conv.nn
-    extra = None
+    extra = bn = None
     if _is_linear(mlp):
         lin = mlp
     else:
         units = [m for m in mlp.children() if type(m).__name__ not in _SKIP] \
             if type(mlp).__name__ == "Sequential" else []
-        shape = [("L" if _is_linear(m) else "A" if _act_name(m) is not None else "?") for m in units]
-        if "".join(shape) not in ("LAL", "LALA"):
-            raise UnsupportedArch("GINConv.nn other than Linear or Sequential(Linear, act, Linear[, act])")
+        shape = [("L" if _is_linear(m) else "A" if _act_name(m) is not None else
+                  "N" if _is_bn(m) else "?") for m in units]
+        if "".join(shape) not in ("LAL", "LALA", "LNAL", "LNALA"):
+            raise UnsupportedArch("GINConv.nn other than Linear or Sequential(Linear, [BatchNorm1d,] "
+                                  "act, Linear[, act])")
         lin = units[0]
+        if shape[1] == "N":
+            bn, units = units[1], units[:1] + units[2:]
         extra = (units[2], _act_name(units[1]), _act_name(units[3]) if len(units) == 4 else None)
     if _lazy(lin) or (extra is not None and _lazy(extra[0])):
         raise UnsupportedArch("GINConv.nn with uninitialised (lazy) weights")
     W = _f32(lin.weight)
     b = _f32(lin.bias) if getattr(lin, "bias", None) is not None else None
     root = ((1.0 + eps) * lin.weight.detach().double()).to(torch.float32)  # folded in fp64, rounded once
+    if bn is not None:
+        s, t = _bn_affine(bn, W.shape[0])
+        root = _fold_rows((1.0 + eps) * lin.weight.detach().double(), s)
+        W, b = _fold_rows(W, s), _fold_bias(b, s, t, W.shape[0])
     return [Term("sum", rel, W)], b, root, W.shape[1], W.shape[0], extra
 
 
@@ -542,12 +658,21 @@ def _head_layers(prog, units, i):
     the first unit past it."""
     while i < len(units) and _is_linear(units[i]):
         lin = units[i]
-        act = None
+        act = norm = None
+        if i + 1 < len(units) and _is_norm(units[i + 1]):
+            norm = units[i + 1]
+            i += 1
         if i + 1 < len(units) and _act_name(units[i + 1]) is not None:
             act = _act_name(units[i + 1])
             i += 1
+        W = _f32(lin.weight)
         b = _f32(lin.bias) if getattr(lin, "bias", None) is not None else None
-        prog.head.append(HeadLayer(_f32(lin.weight), b, act))
+        if norm is not None:
+            if not _is_bn(norm):
+                raise UnsupportedArch("LayerNorm after a head Linear")
+            s, t = _bn_affine(norm, W.shape[0])
+            W, b = _fold_rows(W, s), _fold_bias(b, s, t, W.shape[0])
+        prog.head.append(HeadLayer(W, b, act))
         i += 1
     return i
 
@@ -609,6 +734,9 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
         prog = compile_arch(arch.encoder, edge_type_names, node_type_names, attention)
         if prog.pool is not None:
             raise UnsupportedArch("LinkModel over a pooled encoder")
+        if prog.has_post:
+            raise UnsupportedArch("LinkModel over an encoder with post-ops (LayerNorm, residual, "
+                                  "BatchNorm after attention)")
         prog.link_act = getattr(arch, "act", "identity") or "identity"
         return prog
     if type(arch).__name__ == "RelLinkModel" and hasattr(arch, "encoder"):
@@ -644,7 +772,12 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
             extra = None
         else:
             terms, bias, f_in, f_out, extra = _conv_layer(units[i], rel_index, attention)
-        act = None
+        act = norm = None
+        if i + 1 < len(units) and _is_norm(units[i + 1]):
+            if multi or type(units[i]).__name__ == "HeteroConv":
+                raise UnsupportedArch(f"{type(units[i + 1]).__name__} after HeteroConv")
+            norm = units[i + 1]
+            i += 1
         if i + 1 < len(units) and _act_name(units[i + 1]) is not None:
             act = _act_name(units[i + 1])
             i += 1
@@ -662,6 +795,8 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
             prog.extra_layers += 1
         else:
             prog.convs.append(ConvLayer(terms, bias, act, f_in, f_out))
+        if norm is not None:
+            _norm_conv_layer(prog.convs[-1], norm)
         i += 1
     if not prog.convs:
         raise UnsupportedArch("arch has no GCNConv/SAGEConv/HeteroConv layer first")
@@ -672,7 +807,26 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
     if i != len(units):
         raise UnsupportedArch(f"unexpected module order at {type(units[i]).__name__}")
     _check_widths(prog)
+    if type(arch).__name__ == "BlockStack" and getattr(arch, "residual", False):
+        _add_residuals(prog)
     return prog
+
+
+def _add_residuals(prog):
+    """nn.BlockStack(residual=True): block i adds its input row to its output where the two widths
+    are equal.  The skip joins the layer's post-op (which takes the activation with it)."""
+    if prog.extra_layers:
+        raise UnsupportedArch("BlockStack(kind='gin', residual=True): the skip would span two program layers")
+    if any(t.kind == "rel" for c in prog.convs for t in c.terms) or prog.n_types > 1:
+        raise UnsupportedArch("residual blocks on typed-relation / multi-node-type programs")
+    for li, c in enumerate(prog.convs):
+        if c.f_in != c.f_out:
+            continue
+        if li == 0:
+            raise UnsupportedArch("a residual on the first block (its input rows are the raw features)")
+        if c.post is None:
+            c.post, c.act = PostOp(act=c.act), None
+        c.post.residual = True
 
 
 def count_message_passing(arch: nn.Module) -> int:

@@ -475,6 +475,65 @@ int xpg_pool_rows(const float* h, int64_t rows, int64_t n, int64_t ld, int32_t k
  * function sharing the launcher's selection; XPG_ENOSPC when `nbytes` do not hold the text. */
 int xpg_pool_describe(int64_t rows, int64_t n, int64_t ld, int32_t kind, char* buf, size_t nbytes);
 
+/* Post-ops of conv layers (v27 addendum: new symbols only; the version, every struct above and the
+ * three entry points above are unchanged, and a library without these symbols fails to load).
+ * One record per conv layer, a HOST array [n_layers] handed beside the plan; an all-zero record
+ * means the layer has no post-op, and post == NULL means no layer has one (then each _post entry
+ * point is its namesake above, same results).  A layer with a post-op carries act = XPG_ACT_NONE
+ * in its xpg_layer_desc; after its bias the post-op works in place on each of the layer's output
+ * rows (one f_out_pad-wide fp32 row per (mask row, target)), in this order:
+ *   1. v = h * scale + shift              (device [f_out_pad] each; NULL = 1 / 0)
+ *   2. norm LAYER: mean and biased variance of v over the f_out real columns, two passes in fp32;
+ *      v = (v - mean) / sqrt(var + eps) * gamma + beta   (device [f_out_pad]; NULL = 1 / 0)
+ *   3. v = act(v)
+ *   4. residual: v += the same mask row's input row of that target, row
+ *      (r * n_prev + tgt_prev[t]) of the previous layer's output (after ITS post-op)
+ *   5. columns f_out .. f_out_pad - 1 are written as exact 0, whatever they held.
+ * A BatchNorm in eval mode that cannot be folded into the layer's weights (attention layers) is
+ * the affine of step 1; a LayerNorm over the last dimension is step 2.  The sums are reduced in a
+ * fixed order that depends on (f_out, f_out_pad) alone: row shards and repeated calls agree bit
+ * for bit.  Host checks, XPG_EINVAL before any launch: a post layer whose xpg_layer_desc.act is
+ * not NONE; norm outside enum xpg_norm; LAYER with eps not finite or <= 0; gamma / beta without
+ * LAYER; residual on layer 1, with f_out_pad unequal to the previous layer's, or without tgt_prev;
+ * an edge_masks or edge_dot plan; n_types > 1 / tgt_type.  A plan with any post-op runs on the
+ * multi-kernel path only (a forced rows / fused / wide path under XPG_FORWARD_STRICT=1 is
+ * refused); when its last conv layer has a post-op, neither the out-column pick nor the first head
+ * layer is fused into that layer's dense epilogue; a pooled plan's readout follows the post-op.
+ * xpg_forward_describe_post writes `unfused` followed by ` post<l>=k_post<NORM,RES>` for each post
+ * layer l (1-based), e.g. `unfused post2=k_post<layer,1>`.  The workspace is that of the same plan
+ * without post-ops on the multi-kernel path. */
+enum xpg_norm { XPG_NORM_NONE = 0, XPG_NORM_LAYER = 1 };
+typedef struct xpg_post_desc {
+  int32_t norm;            /* enum xpg_norm                                              */
+  float eps;               /* LAYER: added to the variance                               */
+  const float* scale;      /* before the norm                                            */
+  const float* shift;
+  const float* gamma;      /* after the norm (LAYER only)                                */
+  const float* beta;
+  int32_t act;             /* enum xpg_act                                               */
+  int32_t residual;        /* 0 / 1                                                      */
+} xpg_post_desc;
+int xpg_forward_workspace_post(const xpg_forward_plan* plan, const xpg_post_desc* post, int64_t rows,
+                               size_t* bytes);
+int xpg_masked_forward_post(const xpg_forward_plan* plan, const xpg_post_desc* post, const uint32_t* bits,
+                            int64_t rows, float* y, void* workspace, size_t workspace_bytes,
+                            xpg_stream_t stream);
+int xpg_forward_describe_post(const xpg_forward_plan* plan, const xpg_post_desc* post, int64_t rows,
+                              char* buf, size_t n);
+/* One post-op on its own: in place on h [M][ld] fp32 (ld % 4 == 0, 4 <= ld <= 256, 1 <= f_out <= ld,
+ * h and the record's arrays ([ld] each) 16-byte aligned).  With post->residual: M = rows * n_tgt,
+ * hprev [rows][n_prev][ld_prev] (ld_prev >= ld, % 4 == 0, 16-byte aligned), tgt_prev device
+ * [n_tgt] with values < n_prev; otherwise hprev / ld_prev / n_tgt / n_prev / tgt_prev are not read.
+ * An item is one row on a power-of-two group of >= ld / 4 lanes of one wave (one float4 chunk per
+ * lane), so a wave works on 64 / group rows at once. */
+int xpg_post_rows(float* h, int64_t M, int64_t ld, int64_t f_out, const xpg_post_desc* post,
+                  const float* hprev, int64_t ld_prev, int64_t n_tgt, int64_t n_prev,
+                  const int32_t* tgt_prev, xpg_stream_t stream);
+/* The kernel xpg_post_rows launches for a shape, as text: `k_post<layer,1> group=8 rows_per_wave=8`.
+ * A HOST function sharing the launcher's selection; XPG_ENOSPC when `nbytes` do not hold the text. */
+int xpg_post_describe(int64_t M, int64_t ld, int64_t f_out, const xpg_post_desc* post, char* buf,
+                      size_t nbytes);
+
 /* Optional per-kernel timing of xpg_masked_forward's wide (full-graph) path (v13): with profiling
  * on, every launch of a profiled kernel is bracketed by two hipEvents on its stream;
  * xpg_profile_read waits for them and returns, per slot, the summed device milliseconds and the
