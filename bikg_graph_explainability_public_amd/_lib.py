@@ -70,6 +70,16 @@ class PostDesc(ctypes.Structure):
                 ("beta", c_vp), ("act", c_i32), ("residual", c_i32)]
 
 
+class LayerWeights(ctypes.Structure):
+    """xpg_layer_weights (v27 addendum): one conv layer's edge weights in the layer's CSR order."""
+    _fields_ = [("agg_w", c_vp), ("self_sum", c_vp), ("self_wmax", c_vp), ("self_wmin", c_vp)]
+
+
+class EdgeWeights(ctypes.Structure):
+    """xpg_edge_weights (v27 addendum): a plan's edge weights; `layers` is a host array."""
+    _fields_ = [("deg_w", c_vp), ("loop_w", c_vp), ("layers", ctypes.POINTER(LayerWeights))]
+
+
 class WlmParams(ctypes.Structure):
     _fields_ = [("lr", c_f32), ("l1_lambda", c_f32), ("beta1", c_f32), ("beta2", c_f32),
                 ("eps", c_f32), ("weight_decay", c_f32)]
@@ -119,6 +129,12 @@ _SIGS = {
                                  c_vp, c_vp, ctypes.c_size_t, c_vp], c_i32),
     "xpg_forward_describe_post": ([ctypes.POINTER(ForwardPlanDesc), ctypes.POINTER(PostDesc), c_i64,
                                    ctypes.c_char_p, ctypes.c_size_t], c_i32),
+    "xpg_forward_workspace_w": ([ctypes.POINTER(ForwardPlanDesc), ctypes.POINTER(PostDesc),
+                                 ctypes.POINTER(EdgeWeights), c_i64, ctypes.POINTER(ctypes.c_size_t)], c_i32),
+    "xpg_masked_forward_w": ([ctypes.POINTER(ForwardPlanDesc), ctypes.POINTER(PostDesc),
+                              ctypes.POINTER(EdgeWeights), c_vp, c_i64, c_vp, c_vp, ctypes.c_size_t, c_vp], c_i32),
+    "xpg_forward_describe_w": ([ctypes.POINTER(ForwardPlanDesc), ctypes.POINTER(PostDesc),
+                                ctypes.POINTER(EdgeWeights), c_i64, ctypes.c_char_p, ctypes.c_size_t], c_i32),
     "xpg_post_rows": ([c_vp, c_i64, c_i64, c_i64, ctypes.POINTER(PostDesc), c_vp, c_i64, c_i64, c_i64,
                        c_vp, c_vp], c_i32),
     "xpg_post_describe": ([c_i64, c_i64, c_i64, ctypes.POINTER(PostDesc), ctypes.c_char_p,

@@ -1096,6 +1096,218 @@ __global__ __launch_bounds__(256) void k_agg(AggArgs a) {
   }
 }
 
+// ------------------------------------------------------------------------------------ edge weights
+// Weighted graphs (xpg_edge_weights; the rules are in xpgnn.h).  Kernels of their own, so that the
+// unweighted k_degree / k_agg / k_agg_l1_rows keep their code and registers.
+// k_degree_w: k_degree's thread mapping and its kin (the COUNT of kept in-edges, -1 for a
+// masked-out node); GCN (plans with a GCN term) also writes kinw, the weighted degree
+// loop_w + sum of the kept in-edges' weights in CSR order, 1 for a masked-out node (its only edge is
+// the weight-1 loop add_remaining_self_loops gives it).
+template <bool GCN>
+__global__ void k_degree_w(const uint32_t* __restrict__ bits, int64_t rows, int words, int n0, int n_deg,
+                           int n_rel, const int32_t* __restrict__ f0_node,
+                           const int32_t* __restrict__ deg_ptr, const int32_t* __restrict__ deg_src,
+                           const float* __restrict__ deg_w, const float* __restrict__ loop_w,
+                           float* __restrict__ kin, float* __restrict__ kinw) {
+  const int64_t per_row = (int64_t)n_rel * n_deg;
+  int64_t idx = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (idx >= rows * per_row) return;
+  const int64_t b = idx / per_row;
+  const int rem = static_cast<int>(idx - b * per_row);
+  const int r = rem / n_deg, p = rem - r * n_deg;
+  const uint32_t* row = bits + b * words;
+  const int* pp = deg_ptr + (int64_t)r * (n0 + 1);
+  float out = -1.f, outw = 1.f;
+  if (bit_of(row, f0_node[p])) {
+    int c = 0;
+    float s = GCN ? loop_w[(int64_t)r * n0 + p] : 0.f;
+    for (int e = pp[p]; e < pp[p + 1]; ++e) {
+      const int k = bit_of(row, deg_src[e]);
+      c += k;
+      if (GCN) {
+        const float w = deg_w[e];
+        s += k ? w : 0.f;
+      }
+    }
+    out = static_cast<float>(c);
+    outw = s;
+  }
+  kin[idx] = out;
+  if (GCN) kinw[idx] = outw;
+}
+
+struct AggWArgs {
+  AggArgs a;              // as k_agg's; agg_eid / bits / tgt_type unset (refused on the host)
+  const float* agg_w;     // [n_edges] weight of each in-edge (the index of agg_f0)
+  const float* self_sum;  // [n_rel * n_tgt] the target's self-loop weights: sum, max, min
+  const float* self_wmax;
+  const float* self_wmin;
+  const float* kinw;      // [rows][n_rel][kpitch] weighted degrees (plans with a GCN term, else null)
+  const float* loop_w;    // [n_rel * n0] last self-loop weight of each F_0 node, else 1
+};
+
+__device__ __forceinline__ float inv_sqrt_wdeg(float d) { return d > 0.f ? 1.f / sqrtf(d) : 0.f; }
+
+// Masked, weighted aggregation for one conv layer: k_agg's item and lane mapping, forms (L1: the
+// tables and the bias + activation epilogue; else one slice of the GEMM input per term) and keep
+// tests (node masks only).  Every term kind walks its in-edges in the staged form: EB edges' weights,
+// keep tests (GCN: also the sources' weighted degrees) and rows are issued before the first fma,
+// and the adds stay in edge order.  The self-loops never are visited: SUM / MEAN add self_sum * x_t,
+// MAX folds them per element (the maximum of w x over the loops is wmax x for x >= 0, else wmin x).
+template <bool L1, int LPS, int NV>
+__global__ __launch_bounds__(256) void k_agg_w(AggWArgs w) {
+  const AggArgs& a = w.a;
+  const int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t item = gid / LPS;
+  const int sub = static_cast<int>(gid - item * LPS);
+  if (item >= a.rows * a.n_tgt) return;
+  const int64_t b = item / a.n_tgt;
+  const int t = static_cast<int>(item - b * a.n_tgt);
+  const float* kb = a.kin + b * (int64_t)a.n_rel * a.kpitch;
+  const float* kwb = w.kinw ? w.kinw + b * (int64_t)a.n_rel * a.kpitch : nullptr;
+  const uint32_t* mrow = a.mbits ? a.mbits + b * a.words : nullptr;
+  const int t0 = a.tgt_f0[t];
+  const int tp = a.tgt_prev[t];
+  float4 tot[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) tot[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+
+  for (int k = 0; k < a.n_terms; ++k) {
+    const int kind = a.kind[k];
+    const int r = a.rel[k];
+    const float* base = L1 ? a.table[k] : a.hprev + b * a.hstride;
+    const int self_pos = L1 ? t0 : tp;
+    const float4* selfrow = reinterpret_cast<const float4*>(base + (int64_t)self_pos * a.width);
+    float4 s[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) s[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (kind == XPG_TERM_ROOT) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j) s[j] = selfrow[sub + j * LPS];
+    } else {
+      const float kt = kb[(int64_t)r * a.kpitch + t0];
+      const bool gcn = kind == XPG_TERM_GCN;
+      const bool mx = !L1 && kind == XPG_TERM_MAX;
+      // a masked-out target keeps nothing but, for GCN, its weight-1 loop (deg = 1)
+      if (kt >= 0.f || gcn) {
+        const int* pp = a.agg_ptr + (int64_t)r * (a.n_tgt + 1);
+        const int64_t ti = (int64_t)r * a.n_tgt + t;
+        const int sm = a.self_mult[ti];
+        float dt = 1.f;
+        bool any = false;
+        if (gcn) {
+          dt = inv_sqrt_wdeg(kwb[(int64_t)r * a.kpitch + t0]);
+          const float lw = kt >= 0.f ? w.loop_w[(int64_t)r * a.n0 + t0] : 1.f;
+          const float cself = dt * dt * lw;
+#pragma unroll
+          for (int j = 0; j < NV; ++j) fma4(s[j], cself, selfrow[sub + j * LPS]);
+        } else if (mx) {
+          any = sm > 0;
+          const float ninf = -__builtin_huge_valf();
+          const float hi = w.self_wmax[ti], lo = w.self_wmin[ti];
+#pragma unroll
+          for (int j = 0; j < NV; ++j) {
+            const float4 x = selfrow[sub + j * LPS];
+            s[j] = any ? make_float4((x.x >= 0.f ? hi : lo) * x.x, (x.y >= 0.f ? hi : lo) * x.y,
+                                     (x.z >= 0.f ? hi : lo) * x.z, (x.w >= 0.f ? hi : lo) * x.w)
+                       : make_float4(ninf, ninf, ninf, ninf);
+          }
+        } else {
+          const float ws = w.self_sum[ti];
+#pragma unroll
+          for (int j = 0; j < NV; ++j) fma4(s[j], ws, selfrow[sub + j * LPS]);
+        }
+        constexpr int EB = NV >= 4 ? 2 : NV == 2 ? 4 : 8;
+        const int e_end = kt >= 0.f ? pp[t + 1] : pp[t];
+        for (int eb = pp[t]; eb < e_end; eb += EB) {
+          bool kp[EB];
+          int up[EB], kx[EB];
+          float c[EB];
+          // stage by stage over the EB edges, so each stage's loads go out together
+#pragma unroll
+          for (int q = 0; q < EB; ++q) {
+            const int e = eb + q < e_end ? eb + q : eb;
+            up[q] = a.agg_f0[e];
+            c[q] = w.agg_w[e];
+          }
+          if (mrow) {
+#pragma unroll
+            for (int q = 0; q < EB; ++q) kx[q] = a.f0_node[up[q]];
+#pragma unroll
+            for (int q = 0; q < EB; ++q) kp[q] = bit_of(mrow, kx[q]);
+          } else {
+#pragma unroll
+            for (int q = 0; q < EB; ++q) kp[q] = kb[(int64_t)r * a.kpitch + up[q]] >= 0.f;
+          }
+          if (gcn) {  // dis[u] * w_e * dis[t]
+#pragma unroll
+            for (int q = 0; q < EB; ++q) c[q] = inv_sqrt_wdeg(kwb[(int64_t)r * a.kpitch + up[q]]) * c[q] * dt;
+          }
+#pragma unroll
+          for (int q = 0; q < EB; ++q) {
+            kp[q] = kp[q] && eb + q < e_end;
+            if (!L1) up[q] = a.agg_src[eb + q < e_end ? eb + q : eb];
+          }
+#pragma unroll
+          for (int q = 0; q < EB; ++q) asm volatile("" ::"v"(up[q]));  // issued here, not sunk into the branches
+          float4 v[EB][NV];
+#pragma unroll
+          for (int q = 0; q < EB; ++q) {
+            const float4* src = reinterpret_cast<const float4*>(base + (int64_t)up[q] * a.width);
+#pragma unroll
+            for (int j = 0; j < NV; ++j) v[q][j] = kp[q] ? src[sub + j * LPS] : make_float4(0.f, 0.f, 0.f, 0.f);
+          }
+#pragma unroll
+          for (int q = 0; q < EB; ++q) {
+            if (kp[q]) {
+              if (mx) {
+                any = true;
+#pragma unroll
+                for (int j = 0; j < NV; ++j)
+                  max4(s[j], make_float4(c[q] * v[q][j].x, c[q] * v[q][j].y, c[q] * v[q][j].z, c[q] * v[q][j].w));
+              } else {
+#pragma unroll
+                for (int j = 0; j < NV; ++j) fma4(s[j], c[q], v[q][j]);
+              }
+            }
+          }
+        }
+        if (mx && !any) {  // torch_scatter's fill for an empty segment
+#pragma unroll
+          for (int j = 0; j < NV; ++j) s[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        if (kind == XPG_TERM_MEAN) {  // the COUNT of kept in-edges, self-loops included
+          const float cnt = kt + static_cast<float>(sm);
+          const float inv = 1.f / (cnt > 1.f ? cnt : 1.f);
+#pragma unroll
+          for (int j = 0; j < NV; ++j) { s[j].x *= inv; s[j].y *= inv; s[j].z *= inv; s[j].w *= inv; }
+        }
+      }
+    }
+    if (L1) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+        tot[j].x += s[j].x; tot[j].y += s[j].y; tot[j].z += s[j].z; tot[j].w += s[j].w;
+      }
+    } else {
+      float4* o = reinterpret_cast<float4*>(a.out + item * a.out_ld + (int64_t)k * a.width);
+#pragma unroll
+      for (int j = 0; j < NV; ++j) o[sub + j * LPS] = s[j];
+    }
+  }
+  if (L1) {
+    float4* o = reinterpret_cast<float4*>(a.out + item * a.out_ld);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      const int f = (sub + j * LPS) * 4;
+      float v[4] = {tot[j].x, tot[j].y, tot[j].z, tot[j].w};
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[q] = (f + q < a.f_real) ? act_apply(v[q] + a.bias[f + q], a.act) : 0.f;
+      o[sub + j * LPS] = make_float4(v[0], v[1], v[2], v[3]);
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------ attention
 // Graph attention (XPG_TERM_ATT, GATConv; the rules are in xpgnn.h).  Layers of ATT terms run on
 // kernels of their own: the per-edge weight depends on the mask row through a softmax over the
@@ -6597,6 +6809,42 @@ int pool_plan_check(const xpg_forward_plan* p) {
   return XPG_OK;
 }
 
+// the host checks of a weighted plan (xpgnn.h, xpg_edge_weights): before any launch, and without
+// reading through a device pointer
+bool plan_has_gcn(const xpg_forward_plan* p) {
+  for (int l = 0; l < p->n_layers; ++l)
+    for (int k = 0; k < p->layers[l].n_terms && k < XPG_MAX_TERMS; ++k)
+      if (p->layers[l].terms[k].kind == XPG_TERM_GCN) return true;
+  return false;
+}
+int weights_plan_check(const xpg_forward_plan* p, const xpg_edge_weights* wts) {
+  if (!wts) return XPG_OK;
+  XPG_REQ(p && p->layers && p->n_layers >= 1 && p->n_layers <= 64, "plan: 1..64 conv layers required");
+  XPG_REQ(!p->edge_masks, "masked_forward: edge weights do not take edge-mask plans (edge_masks)");
+  XPG_REQ(!p->edge_dot, "masked_forward: edge weights do not take a link decoder (edge_dot)");
+  XPG_REQ(p->n_rel == 1, "masked_forward: edge weights take one relation (n_rel > 1)");
+  XPG_REQ(wts->layers != nullptr, "masked_forward: edge weights without their layer records");
+  for (int l = 0; l < p->n_layers; ++l) {
+    const xpg_layer_desc& ly = p->layers[l];
+    XPG_REQ(ly.tgt_type == nullptr && ly.n_types <= 1,
+            "masked_forward: edge weights do not take multi-node-type plans (tgt_type)");
+    XPG_REQ(ly.n_terms >= 1 && ly.n_terms <= XPG_MAX_TERMS, "layer: 1..8 terms");
+    for (int k = 0; k < ly.n_terms; ++k) {
+      const int kind = ly.terms[k].kind;
+      XPG_REQ(kind == XPG_TERM_GCN || kind == XPG_TERM_MEAN || kind == XPG_TERM_ROOT || kind == XPG_TERM_SUM ||
+                  kind == XPG_TERM_MAX,
+              "masked_forward: edge weights take GCN / MEAN / SUM / MAX / ROOT terms only (no ATT / ATT2 / REL)");
+    }
+    const xpg_layer_weights& lw = wts->layers[l];
+    XPG_REQ(lw.agg_w && lw.self_sum && lw.self_wmax && lw.self_wmin,
+            "masked_forward: edge weights: a layer record misses agg_w / self_sum / self_wmax / self_wmin");
+  }
+  if (plan_has_gcn(p))
+    XPG_REQ(wts->loop_w && (wts->deg_w || p->n_deg_edges == 0),
+            "masked_forward: edge weights: a GCN term needs deg_w and loop_w");
+  return XPG_OK;
+}
+
 // node-type-gated terms (multi-node-type HeteroConv) run on the multi-kernel path only
 bool plan_multi_type(const xpg_forward_plan* p) {
   for (int l = 0; l < p->n_layers; ++l)
@@ -6716,9 +6964,10 @@ struct WsLayout {
   size_t kin = 0, agg = 0, head0 = 0, head1 = 0, score = 0, xlr = 0, ctl = 0, total = 0;
   size_t h[64];
   size_t pool = 0, pool_part = 0, pool_part_bytes = 0;  // pooled plans only: the region after ctl
+  size_t kinw = 0;  // weighted plans with a GCN term only: the weighted degrees, the last region
 };
 
-int layout_ws(const xpg_forward_plan* p, int64_t rows, WsLayout* L) {
+int layout_ws(const xpg_forward_plan* p, int64_t rows, WsLayout* L, const xpg_edge_weights* wts = nullptr) {
   XPG_REQ(p && p->n_layers >= 1 && p->n_layers <= 64, "plan: 1..64 conv layers required");
   if (const int rc = pool_plan_check(p)) return rc;
   if (const int rc = att2_plan_check(p)) return rc;
@@ -6773,6 +7022,10 @@ int layout_ws(const xpg_forward_plan* p, int64_t rows, WsLayout* L) {
     L->pool_part = off;
     L->pool_part_bytes = pool_partial_bytes(rows, pick.parts, last.f_out_pad);
     off += align_up(L->pool_part_bytes);
+  }
+  if (wts && plan_has_gcn(p)) {  // k_degree_w's second output, kin's shape
+    L->kinw = off;
+    off += align_up(sizeof(float) * (size_t)rows * p->n_rel * deg_pitch(p));
   }
   L->total = off;
   return XPG_OK;
@@ -6857,6 +7110,27 @@ int launch_agg(const AggArgs& a, hipStream_t st) {
   // widths that are odd multiples of 32 below 256 (e.g. 96) map to lps = f4 (non power of 2)
   XPG_AGG(24, 1) XPG_AGG(40, 1) XPG_AGG(48, 1) XPG_AGG(56, 1)
 #undef XPG_AGG
+  return fail(XPG_EINVAL, "agg: unsupported row width " + std::to_string(a.width));
+}
+
+// k_agg_w for one layer of a weighted plan: launch_agg's generic lane mapping (no rows-as-lanes
+// layer-1 kernel)
+template <bool L1>
+int launch_agg_w(const AggWArgs& w, hipStream_t st) {
+  const AggArgs& a = w.a;
+  XPG_REQ(a.width % 32 == 0 && a.width > 0, "agg: row width must be a positive multiple of 32");
+  const int f4 = a.width / 4;
+  const int lps = f4 >= 64 ? 64 : f4;
+  const int nv = f4 / lps;
+  XPG_REQ(f4 % lps == 0 && (nv == 1 || nv == 2 || nv == 4), "agg: unsupported row width");
+  const int64_t threads = a.rows * a.n_tgt * lps;
+  if (threads == 0) return XPG_OK;
+  dim3 grid(static_cast<unsigned>(cdiv(threads, 256))), block(256);
+#define XPG_AGG_W(LPS, NV) \
+  if (lps == LPS && nv == NV) { hipLaunchKernelGGL((k_agg_w<L1, LPS, NV>), grid, block, 0, st, w); XPG_LAUNCHED(); return XPG_OK; }
+  XPG_AGG_W(8, 1) XPG_AGG_W(16, 1) XPG_AGG_W(32, 1) XPG_AGG_W(64, 1) XPG_AGG_W(64, 2) XPG_AGG_W(64, 4)
+  XPG_AGG_W(24, 1) XPG_AGG_W(40, 1) XPG_AGG_W(48, 1) XPG_AGG_W(56, 1)
+#undef XPG_AGG_W
   return fail(XPG_EINVAL, "agg: unsupported row width " + std::to_string(a.width));
 }
 
@@ -8321,13 +8595,21 @@ int xpg_forward_workspace(const xpg_forward_plan* plan, int64_t rows, size_t* by
 // The post-ops work in place on the layers' output rows: the layout is that of the same plan
 // without them, on the multi-kernel path.
 int xpg_forward_workspace_post(const xpg_forward_plan* plan, const xpg_post_desc* post, int64_t rows, size_t* bytes) {
+  return xpg_forward_workspace_w(plan, post, nullptr, rows, bytes);
+}
+
+// Edge weights add the weighted degrees of a GCN plan at the end of that layout.
+int xpg_forward_workspace_w(const xpg_forward_plan* plan, const xpg_post_desc* post, const xpg_edge_weights* wts,
+                            int64_t rows, size_t* bytes) {
+  int rc = weights_plan_check(plan, wts);
+  if (rc) return rc;
   WsLayout L;
-  int rc = layout_ws(plan, rows, &L);
+  rc = layout_ws(plan, rows, &L, wts);
   if (rc) return rc;
   rc = post_plan_check(plan, post);
   if (rc) return rc;
   WideWs W;
-  if (!plan_has_post(plan, post) && wide_wanted(plan) && wide_layout(plan, rows, &W) == 0) {
+  if (!plan_has_post(plan, post) && !wts && wide_wanted(plan) && wide_layout(plan, rows, &W) == 0) {
     *bytes = W.total;  // 32-row passes: one buffer set, or two when rows > 32
     return XPG_OK;
   }
@@ -8341,10 +8623,17 @@ int xpg_forward_describe(const xpg_forward_plan* p, int64_t rows, char* buf, siz
 
 int xpg_forward_describe_post(const xpg_forward_plan* p, const xpg_post_desc* post, int64_t rows, char* buf,
                               size_t n) {
+  return xpg_forward_describe_w(p, post, nullptr, rows, buf, n);
+}
+
+int xpg_forward_describe_w(const xpg_forward_plan* p, const xpg_post_desc* post, const xpg_edge_weights* wts,
+                           int64_t rows, char* buf, size_t n) {
   XPG_REQ(buf != nullptr && n > 0, "forward_describe: no buffer");
   buf[0] = 0;
+  int rc = weights_plan_check(p, wts);
+  if (rc) return rc;
   WsLayout L;
-  int rc = layout_ws(p, rows, &L);
+  rc = layout_ws(p, rows, &L, wts);
   if (rc) return rc;
   XPG_REQ(p->n_rel >= 1 && p->n0 >= 1 && p->cols > 0, "masked_forward: bad plan sizes");
   rc = post_plan_check(p, post);
@@ -8352,10 +8641,11 @@ int xpg_forward_describe_post(const xpg_forward_plan* p, const xpg_post_desc* po
   const bool has_post = plan_has_post(p, post);
   WideWs W;
   FwdPath path;
-  rc = forward_route(p, rows, &W, &path, nullptr, has_post);
+  rc = forward_route(p, rows, &W, &path, nullptr, has_post || wts != nullptr);
   if (rc) return rc;
   if (path == kPathNone) return fail(XPG_EINVAL, kStrictMsg);
   std::string s = kPathName[path];
+  if (wts) s += " weights=k_degree_w+k_agg_w";  // a weighted plan's degree and aggregation kernels
   if (path == kPathWide) {
     WidePick pick;
     rc = wide_select(p, W, &pick);
@@ -8433,8 +8723,16 @@ int xpg_masked_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t 
 
 int xpg_masked_forward_post(const xpg_forward_plan* p, const xpg_post_desc* post, const uint32_t* bits, int64_t rows,
                             float* y, void* workspace, size_t workspace_bytes, xpg_stream_t stream) {
+  return xpg_masked_forward_w(p, post, nullptr, bits, rows, y, workspace, workspace_bytes, stream);
+}
+
+int xpg_masked_forward_w(const xpg_forward_plan* p, const xpg_post_desc* post, const xpg_edge_weights* wts,
+                         const uint32_t* bits, int64_t rows, float* y, void* workspace, size_t workspace_bytes,
+                         xpg_stream_t stream) {
+  int rc = weights_plan_check(p, wts);
+  if (rc) return rc;
   WsLayout L;
-  int rc = layout_ws(p, rows, &L);
+  rc = layout_ws(p, rows, &L, wts);
   if (rc) return rc;
   XPG_REQ(p->n_rel >= 1 && p->n0 >= 1 && p->cols > 0, "masked_forward: bad plan sizes");
   rc = post_plan_check(p, post);
@@ -8451,7 +8749,7 @@ int xpg_masked_forward_post(const xpg_forward_plan* p, const xpg_post_desc* post
   // hold (a wide plan returns before `go` is read; its workspace is checked below)
   const bool ready = workspace_bytes >= L.total && rows != 0;
   const FwdLaunch go{bits, y, st, workspace ? reinterpret_cast<int*>(static_cast<char*>(workspace) + L.ctl) : nullptr};
-  rc = forward_route(p, rows, &W, &path, ready ? &go : nullptr, has_post);
+  rc = forward_route(p, rows, &W, &path, ready ? &go : nullptr, has_post || wts != nullptr);
   if (rc) return rc;
   if (path == kPathWide) {
     XPG_REQ(workspace_bytes >= W.total, "masked_forward: workspace too small");
@@ -8494,10 +8792,33 @@ int xpg_masked_forward_post(const xpg_forward_plan* p, const xpg_post_desc* post
   if (plan_needs_degree(p)) {
     const int64_t n = rows * (int64_t)p->n_rel * kpitch;
     XPG_REQ(!p->edge_masks || p->deg_eid || p->n_deg_edges == 0, "masked_forward: edge-mask plan without deg_eid");
-    hipLaunchKernelGGL(k_degree, dim3(static_cast<unsigned>(cdiv(n, 256))), dim3(256), 0, st, bits, rows, words, p->n0,
-                       kpitch, p->n_rel, p->f0_node, p->deg_ptr, p->deg_src, p->edge_masks ? p->deg_eid : nullptr, kin);
+    if (wts && plan_has_gcn(p))
+      hipLaunchKernelGGL(k_degree_w<true>, dim3(static_cast<unsigned>(cdiv(n, 256))), dim3(256), 0, st, bits, rows,
+                         words, p->n0, kpitch, p->n_rel, p->f0_node, p->deg_ptr, p->deg_src, wts->deg_w, wts->loop_w,
+                         kin, reinterpret_cast<float*>(ws + L.kinw));
+    else if (wts)
+      hipLaunchKernelGGL(k_degree_w<false>, dim3(static_cast<unsigned>(cdiv(n, 256))), dim3(256), 0, st, bits, rows,
+                         words, p->n0, kpitch, p->n_rel, p->f0_node, p->deg_ptr, p->deg_src, nullptr, nullptr, kin,
+                         nullptr);
+    else
+      hipLaunchKernelGGL(k_degree, dim3(static_cast<unsigned>(cdiv(n, 256))), dim3(256), 0, st, bits, rows, words,
+                         p->n0, kpitch, p->n_rel, p->f0_node, p->deg_ptr, p->deg_src,
+                         p->edge_masks ? p->deg_eid : nullptr, kin);
     XPG_LAUNCHED();
   }
+  // a layer's aggregation: k_agg / k_agg_l1_rows, or k_agg_w with the layer's weights
+  auto agg_launch = [&](const AggArgs& a, bool l1, int l) -> int {
+    if (!wts) return l1 ? launch_agg<true>(a, st) : launch_agg<false>(a, st);
+    AggWArgs w;
+    w.a = a;
+    w.agg_w = wts->layers[l].agg_w;
+    w.self_sum = wts->layers[l].self_sum;
+    w.self_wmax = wts->layers[l].self_wmax;
+    w.self_wmin = wts->layers[l].self_wmin;
+    w.kinw = plan_has_gcn(p) ? reinterpret_cast<const float*>(ws + L.kinw) : nullptr;
+    w.loop_w = wts->loop_w;
+    return l1 ? launch_agg_w<true>(w, st) : launch_agg_w<false>(w, st);
+  };
   // one conv layer: its rows into ws + L.h[l] (XPG_REQ and the launchers return from the lambda)
   auto run_layer = [&](int l) -> int {
     const xpg_layer_desc& ly = p->layers[l];
@@ -8605,7 +8926,7 @@ int xpg_masked_forward_post(const xpg_forward_plan* p, const xpg_post_desc* post
       a.width = ly.f_in_pad;
       a.out = agg;
       a.out_ld = (int64_t)ly.n_terms * ly.f_in_pad;
-      rc = launch_agg<false>(a, st);
+      rc = agg_launch(a, false, l);
       if (rc) return rc;
       rc = launch_dense(agg, rows * ly.n_tgt, a.out_ld, ly.weight, a.out_ld, a.out_ld, ly.bias, ly.f_out,
                         ly.f_out_pad, ly.act, hout, ly.f_out_pad, st, ly.tgt_type, ly.n_tgt, ly.f_out_pad, nullptr);
@@ -8617,7 +8938,7 @@ int xpg_masked_forward_post(const xpg_forward_plan* p, const xpg_post_desc* post
       a.bias = ly.bias;
       a.act = ly.act;
       a.f_real = ly.f_out;
-      rc = launch_agg<true>(a, st);
+      rc = agg_launch(a, true, l);
       if (rc) return rc;
     } else {
       const xpg_layer_desc& prev = p->layers[l - 1];
@@ -8628,7 +8949,7 @@ int xpg_masked_forward_post(const xpg_forward_plan* p, const xpg_post_desc* post
       a.width = ly.f_in_pad;
       a.out = agg;
       a.out_ld = (int64_t)ly.n_terms * ly.f_in_pad;
-      rc = launch_agg<false>(a, st);
+      rc = agg_launch(a, false, l);
       if (rc) return rc;
       const bool fuse_here = fuse_out && p->n_head == 1 && l == p->n_layers - 1;
       rc = launch_dense(agg, rows * ly.n_tgt, a.out_ld, ly.weight, a.out_ld, a.out_ld, ly.bias, ly.f_out,

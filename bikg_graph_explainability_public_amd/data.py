@@ -145,15 +145,22 @@ class Data:
 
     # -------------------------------------------------------------- computational graph
     def comp_graph(self, ind, n_hops, problem, names, node_types=None, edge_types=None,
-                   return_pos=False):
+                   return_pos=False, edge_weight=None):
         """data.py:281-361 — k-hop computational subgraph with one hop more than the model.
-        `return_pos` appends the positions of `sub_names` in `names` (int64 numpy array)."""
+        `return_pos` appends the positions of `sub_names` in `names` (int64 numpy array);
+        `edge_weight` ([E]) appends, last, the kept edges' weights (the edge mask that slices
+        `edge_types`; weight 1 for the self-loop a subgraph without edges is given)."""
         hops = n_hops + 1
         n = self.feat.shape[0]
         subset, sub_ei, sub_ind, emask = k_hop_subgraph(ind, hops, self.edge_index, n)
+        sub_w = None
+        if edge_weight is not None:
+            sub_w = edge_weight.reshape(-1)[torch.where(emask)[0]]
         if sub_ei.shape[1] == 0:  # no kept edge (sub_ei has one column per kept edge)
             sub_ei = torch.tensor([[int(sub_ind)], [int(sub_ind)]], dtype=torch.long,
                                   device=self.edge_index.device)
+            if sub_w is not None:
+                sub_w = torch.ones(1, dtype=sub_w.dtype, device=sub_w.device)
         sub_feat = self.feat[subset]
         sub_nt = node_types[subset] if node_types is not None else None
         sub_et = edge_types[torch.where(emask)[0]] if edge_types is not None else None
@@ -162,9 +169,8 @@ class Data:
         # names are converted here, not every name of the graph (1M of them at c3)
         pos = pos.cpu().numpy()
         sub_names = take_names(names, pos)
-        if return_pos:
-            return sub_feat, sub_ei, sub_names, sub_ind, sub_nt, sub_et, pos
-        return sub_feat, sub_ei, sub_names, sub_ind, sub_nt, sub_et
+        out = (sub_feat, sub_ei, sub_names, sub_ind, sub_nt, sub_et) + ((pos,) if return_pos else ())
+        return out + (sub_w,) if edge_weight is not None else out
 
     def edge_comp_graph(self, ind, n_hops, names, return_pos=False):
         """Computational graph of an edge problem (edge masks mode; the reference's data.py:281-361
@@ -210,12 +216,15 @@ class Data:
         tiled = ei.int().repeat(1, B) + off
         return keep, tiled
 
-    def perturb_node(self, mask, edge_type=None):
-        """data.py:453-498."""
+    def perturb_node(self, mask, edge_type=None, edge_weight=None):
+        """data.py:453-498.  With `edge_weight` ([E], one per edge) a third value is returned:
+        the kept edges' weights, in the kept edges' order."""
         keep, tiled = self.build_edge_mask(mask)
         et = None
         if edge_type is not None:
             et = edge_type.int().repeat(mask.shape[0])[keep]
+        if edge_weight is not None:
+            return tiled[:, keep], et, edge_weight.reshape(-1).to(mask.device).repeat(mask.shape[0])[keep]
         return tiled[:, keep], et
 
     def perturb_edge(self, mask, edge_type=None):
@@ -234,9 +243,15 @@ class Data:
         """data.py:556-589."""
         return self.feat.repeat(n, 1), (node_type.repeat(n) if node_type is not None else None)
 
-    def perturbator(self, mask, problem, node_type=None, edge_type=None):
-        """data.py:591-648 — B-fold union graph of the masked copies (generic black-box path)."""
+    def perturbator(self, mask, problem, node_type=None, edge_type=None, edge_weight=None):
+        """data.py:591-648 — B-fold union graph of the masked copies (generic black-box path).
+        With `edge_weight` (node masks only) the kept edges' weights are returned as a fifth value."""
         feat, nt = self.concat_features(mask.shape[0], node_type)
+        if edge_weight is not None:
+            if "edge" in problem:
+                raise NotImplementedError("edge_weight under edge masks is not supported")
+            ei, et, ew = self.perturb_node(mask, edge_type, edge_weight)
+            return feat.float(), nt, ei, et, ew
         if "edge" in problem:
             ei, et = self.perturb_edge(mask, edge_type)
         else:

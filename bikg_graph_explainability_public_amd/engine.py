@@ -725,6 +725,66 @@ def plan_arrays_numpy(S, rel_np, queries, L, rel_eid=None):
             "deg_eid": deg_eid, "layers": layers}
 
 
+WEIGHT_KINDS = ("gcn", "mean", "sum", "max", "root")  # term kinds a weighted plan takes
+
+
+def check_edge_weight(edge_weight, n_edges, gcn):
+    """float32 numpy [n_edges] copy of `edge_weight`: one finite weight per edge, none negative
+    when the program holds a GCN term (gcn_norm's deg^-1/2); ValueError otherwise."""
+    w = np.asarray(torch.as_tensor(edge_weight).detach().cpu().numpy())
+    if w.ndim == 2 and w.shape[1] == 1:
+        w = w[:, 0]
+    if w.ndim != 1 or w.shape[0] != int(n_edges):
+        raise ValueError(f"edge_weight must give one weight per edge ({int(n_edges)}), got shape "
+                         f"{tuple(w.shape)}")
+    if not np.issubdtype(w.dtype, np.floating):
+        raise ValueError("edge_weight must be a floating-point tensor")
+    if not np.isfinite(w).all():
+        raise ValueError("edge_weight must be finite (NaN or inf found)")
+    if gcn and w.size and float(w.min()) < 0:
+        raise ValueError("edge_weight must be >= 0 for GCNConv (gcn_norm takes deg^-1/2)")
+    return np.ascontiguousarray(w, dtype=np.float32)
+
+
+def weight_arrays(arr, src, dst, w):
+    """The edge weights of a plan in its CSR orders (xpgnn.h, xpg_edge_weights), on the host.
+    `arr`: plan_arrays(..., rel_eid=[arange(E)]) of a one-relation graph, so that deg_eid / agg_eid
+    / self_eid are edge ids; src / dst [E] the subgraph's edges, w [E] their weights.  Returns
+    {"deg_w" [n_deg_edges], "loop_w" [n0], "layers": [{"agg_w" [n_edges], "self_sum", "self_wmax",
+    "self_wmin" [n_tgt]}]}, float32: loop_w = the weight of a node's LAST self-loop in edge order (1
+    without one), self_* = sum / max / min over the target's self-loops (sum 0, max / min 1 without
+    one; the sum is taken in fp64 and rounded once)."""
+    w = np.asarray(w, dtype=np.float32)
+    src, dst = np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)
+    fr0 = np.asarray(arr["frontiers"][0], dtype=np.int64)
+    S = int(max(src.max(initial=-1), dst.max(initial=-1), fr0.max(initial=-1))) + 1
+    lw = np.ones(S, dtype=np.float32)
+    loops = np.nonzero(src == dst)[0]
+    if loops.size:
+        # the last loop of each node by edge position: the first occurrence in reversed order
+        rev = loops[::-1]
+        nodes, first = np.unique(src[rev], return_index=True)
+        lw[nodes] = w[rev[first]]
+    out = {"deg_w": w[np.asarray(arr["deg_eid"], dtype=np.int64)], "loop_w": lw[fr0], "layers": []}
+    for lay in arr["layers"]:
+        sptr = np.asarray(lay["self_ptr"], dtype=np.int64)
+        ws = w[np.asarray(lay["self_eid"], dtype=np.int64)]
+        n_t = sptr.size - 1
+        cnt = np.diff(sptr)
+        seg = np.repeat(np.arange(n_t), cnt)
+        ssum = np.zeros(n_t, dtype=np.float64)
+        np.add.at(ssum, seg, ws.astype(np.float64))
+        smax = np.full(n_t, -np.inf, dtype=np.float32)
+        smin = np.full(n_t, np.inf, dtype=np.float32)
+        np.maximum.at(smax, seg, ws)
+        np.minimum.at(smin, seg, ws)
+        smax[cnt == 0] = 1.0
+        smin[cnt == 0] = 1.0
+        out["layers"].append({"agg_w": w[np.asarray(lay["agg_eid"], dtype=np.int64)],
+                              "self_sum": ssum.astype(np.float32), "self_wmax": smax, "self_wmin": smin})
+    return out
+
+
 _STAGING = {}  # device index -> [next slot, [(pinned host tensor, event of its last copy)] * _STAGING_SLOTS]
 _STAGING_MAX = 16 << 20  # bytes: larger arrays take the pageable copy
 _STAGING_SLOTS = 4  # a call's uploads take consecutive slots: none waits for the previous copy
@@ -822,7 +882,7 @@ class ForwardPlan:
     """Receptive-field plan of one (subgraph, model program, query set)."""
 
     def __init__(self, program, sub_feat, rel_edges, queries, device=None, node_type=None,
-                 edge_cols=None, link=None):
+                 edge_cols=None, link=None, edge_weight=None):
         """`node_type` ([S] node type of every subgraph node) is required by multi-node-type
         programs: per layer, every target's type gates the relation terms (xpgnn.h).
 
@@ -837,7 +897,13 @@ class ForwardPlan:
         A pooled program (`program.pool`, nn.PooledModel): after the last conv layer the rows of
         the `queries` (pipeline.build_plan passes every node) reduce to one row per mask row
         (xpg_layer_desc.pool), the head runs on it and forward returns [rows, 1]; node masks,
-        single-node-type programs only."""
+        single-node-type programs only.
+
+        `edge_weight` ([E], one finite float per edge of the one relation; PyG 2.0.4's edge_weight
+        of GCNConv / GraphConv): the plan carries the weights gathered into its CSR orders
+        (weight_arrays; xpgnn.h, xpg_edge_weights) and runs on k_degree_w / k_agg_w.  Node masks,
+        one relation, one node type, gcn / mean / sum / max / root terms only; weights >= 0 with a
+        gcn term.  None: the plan is exactly the unweighted one."""
         device = torch.device(device) if device is not None else sub_feat.device
         _lib.require_device(torch.empty(0, device=device), "plan device")
         if len(program.convs) == 0:
@@ -880,6 +946,19 @@ class ForwardPlan:
             if ncol == 0:
                 raise ValueError("edge masks need at least one edge")
         L = len(program.convs)
+        w_np = None
+        if edge_weight is not None:
+            kinds = {t.kind for c in program.convs for t in c.terms}
+            if not kinds <= set(WEIGHT_KINDS):
+                raise ValueError(f"edge_weight on a program with {sorted(kinds - set(WEIGHT_KINDS))} "
+                                 "terms is not supported (GCNConv / GraphConv only)")
+            if self.edge_masks or link is not None:
+                raise ValueError("edge_weight on edge-mask plans is not supported")
+            if self.n_rel != 1 or program.n_types > 1:
+                raise ValueError("edge_weight on multi-relation or multi-node-type graphs is not supported")
+            w_np = check_edge_weight(edge_weight, rel_np[0].shape[1], "gcn" in kinds)
+            # the CSRs carry each entry's edge id, which gathers the weights below
+            rel_eid = [np.arange(rel_np[0].shape[1], dtype=np.int64)]
         arr = plan_arrays(S, rel_np, queries, L, rel_eid)
         self.arrays = arr
         fr = arr["frontiers"]
@@ -1218,6 +1297,28 @@ class ForwardPlan:
         if self.pool is not None:
             self.n_out = 1  # forward returns [rows, 1], as link plans do
         self._upload_i32()
+        # edge weights (xpgnn.h, xpg_edge_weights): every array in one upload
+        self._weights = None
+        self.weight_arrays = None
+        if w_np is not None:
+            wa = weight_arrays(arr, rel_np[0][0], rel_np[0][1], w_np)
+            self.weight_arrays = wa
+            nz = lambda a: a if a.size else np.zeros(1, np.float32)
+            parts = [nz(wa["deg_w"]), nz(wa["loop_w"])]
+            for lay in wa["layers"]:
+                parts += [nz(lay[k]) for k in ("agg_w", "self_sum", "self_wmax", "self_wmin")]
+            offs = np.concatenate([[0], np.cumsum([(a.size + 15) // 16 * 16 for a in parts])]).astype(np.int64)
+            host = np.zeros(int(offs[-1]), dtype=np.float32)
+            for a, o in zip(parts, offs):
+                host[o:o + a.size] = a
+            buf = h2d(host, device)
+            self._keep.append(buf)
+            at = lambda i: buf.data_ptr() + 4 * int(offs[i])
+            self._layer_weights = (_lib.LayerWeights * L)()
+            for li in range(L):
+                lw = self._layer_weights[li]
+                lw.agg_w, lw.self_sum, lw.self_wmax, lw.self_wmin = (at(2 + 4 * li + j) for j in range(4))
+            self._weights = _lib.EdgeWeights(deg_w=at(0), loop_w=at(1), layers=self._layer_weights)
         self._ws = None
         self._ws_stream = None  # raw handle of the stream that last used self._ws
 
@@ -1260,6 +1361,8 @@ class ForwardPlan:
     def _entry(self, name):
         """The entry point and its leading arguments: `name`(plan, ...), or with post-ops
         `name`_post(plan, post records, ...)."""
+        if self._weights is not None:  # `name`_w(plan, post records or NULL, weights, ...)
+            return name + "_w", (ctypes.byref(self.desc), self._post, ctypes.byref(self._weights))
         if self._post is None:
             return name, (ctypes.byref(self.desc),)
         return name + "_post", (ctypes.byref(self.desc), self._post)
@@ -1274,7 +1377,7 @@ class ForwardPlan:
         """The path forward() takes for `rows` mask rows under the current environment: "rows",
         "fused", "unfused", or "wide l1=<kernel> l2=<kernel>" with the kernels' template
         arguments; a plan with post-ops: "unfused post<l>=k_post<NORM,RES> ..." (each post layer's
-        kernel).  A host query of the library's own dispatch (nothing is launched); raises
+        kernel); a weighted plan: "unfused weights=k_degree_w+k_agg_w" before those tokens.  A host query of the library's own dispatch (nothing is launched); raises
         where forward() would refuse the plan (XPG_FORWARD_STRICT=1)."""
         buf = ctypes.create_string_buffer(1024)
         name, lead = self._entry("xpg_forward_describe")

@@ -73,7 +73,7 @@ def set_seed(seed=100):
 class Explainer:
     def __init__(self, feat, edge_index, arch, params, names, pathways=None, pathway_names=None,
                  element_type=None, problem="node_prediction", node_types=None,
-                 edge_types=None):
+                 edge_types=None, edge_weight=None):
         self.initial_assertions(feat, edge_index, arch, params, names, pathways, pathway_names,
                                 element_type, problem)
         self.feat = feat
@@ -87,10 +87,13 @@ class Explainer:
         self.problem = problem.lower().strip()
         self.node_types = node_types
         self.edge_types = edge_types
+        self.edge_weight = edge_weight
         self.last_run = None  # diagnostics of the last run (per-repeat losses, path used)
         self.group = None     # torch.distributed process group for multi-GPU runs (None = world)
         self._verified = set()  # module states whose compiled program passed verify_plan
         self._queries = {}      # per-query (prepare context, plan, arch check): _query_key
+        if edge_weight is not None:
+            self._check_edge_weight()
         if self.pooled:
             if "graph" not in self.problem:
                 raise ValueError(f"arch.forward takes three parameters (x, edge_index, batch): that "
@@ -109,6 +112,23 @@ class Explainer:
         graph's own prediction, one output per perturbed copy.  `element` is still validated
         against `names` as the reference validates it, and selects nothing."""
         return pipeline.pooled_call(self.arch)
+
+    def _check_edge_weight(self):
+        """`edge_weight` ([E] float tensor, one finite weight per edge; PyG 2.0.4's edge_weight of
+        GCNConv / GraphConv): node_prediction and graph_prediction on homogeneous tensors.  The
+        arch is called `arch(x, edge_index[, batch], edge_weight=w)` with each perturbed copy's
+        kept edges' weights; on the engine the plan carries them (k_degree_w / k_agg_w)."""
+        if isinstance(self.feat, dict) or isinstance(self.edge_index, dict):
+            raise NotImplementedError("edge_weight: homogeneous tensors only (no hetero dict graphs)")
+        if self.node_types is not None or self.edge_types is not None or self.element_type is not None:
+            raise NotImplementedError("edge_weight with node_types / edge_types is not supported")
+        if "edge" in self.problem or "link" in self.problem or bool(self.params.get("edge_masks", False)):
+            raise NotImplementedError("edge_weight under edge masks / link_prediction is not supported "
+                                      "(node_prediction and graph_prediction only)")
+        if not isinstance(self.edge_weight, torch.Tensor):
+            raise TypeError("edge_weight must be a torch tensor with one weight per edge")
+        pipeline.require_edge_weight_arch(self.arch)
+        pipeline.checked_edge_weight(self.arch, self.edge_weight, self.edge_index.shape[1])
 
     @property
     def attention_engine(self):
@@ -225,7 +245,7 @@ class Explainer:
         return (id(self.arch), state[0], state[1], self.edge_masks, self.attention_engine,
                 bool(getattr(plan, "multi_type", False)),
                 tuple(c["h_ntypes"] or ()), tuple(c["h_etypes"] or ()),
-                tuple(getattr(plan, "lowering", ())))
+                tuple(getattr(plan, "lowering", ())), self.edge_weight is not None)
 
     def _query_key(self, element, device):
         """The cache slot of a query: element, problem, device and modes.  Whether the slot's
@@ -234,7 +254,7 @@ class Explainer:
         stream as the reference's)."""
         return (str(element), type(element).__name__, self.problem, self.edge_masks, str(device),
                 _freeze(self.element_type), str(self.params.get("verify_arch", True)),
-                self.attention_engine)
+                self.attention_engine, self.edge_weight is not None)
 
     def _query_sources(self, params, bufs):
         """Identity snapshot of what prepare() and the query's ForwardPlan read: the graph and
@@ -243,7 +263,7 @@ class Explainer:
         pathways inputs and the module (identity), the module's parameters and buffers."""
         return _snapshot((self.feat, self.edge_index, self.node_types, self.edge_types,
                           self.names, self.pathways, self.pathway_names, self.arch,
-                          tuple(params), tuple(bufs)))
+                          tuple(params), tuple(bufs), self.edge_weight))
 
     def _query_fingerprints(self):
         """Full-content fingerprints of the inputs read in full by prepare(): pathways and
@@ -291,7 +311,8 @@ class Explainer:
             nonlocal user
             if "bytes" not in e:
                 if user is None:
-                    user = _tensor_ptrs((self.feat, self.edge_index, self.node_types, self.edge_types))
+                    user = _tensor_ptrs((self.feat, self.edge_index, self.node_types, self.edge_types,
+                                         self.edge_weight))
                 ctx = sum(t.numel() * t.element_size() for t in e["c"].values()
                           if isinstance(t, torch.Tensor) and t.data_ptr() not in user)
                 e["bytes"] = ctx + (e["plan"].device_bytes() if e["plan"] is not None else 0)
@@ -329,7 +350,11 @@ class Explainer:
         data = Data(feat, ei)
         sub_pw = sub_pw_names = None
         sub_nt = sub_et = None
-        link = pos = label_type = None
+        link = pos = label_type = sub_w = None
+        ew = None
+        if self.edge_weight is not None:
+            self._check_edge_weight()  # again: the tensor may have been edited in place
+            ew = self.edge_weight.reshape(-1).to(device=device, dtype=torch.float32)
         if self.edge_masks:
             # edge problem, edge masks (non-compat: the reference's edge path is broken at
             # masks.py:294 and data.py:331): mask columns = the computational graph's edges
@@ -356,8 +381,13 @@ class Explainer:
             rels = len(h_etypes) if h_etypes is not None else 0
             n_hops = Model(self.arch).get_hops(rels)
             ind = self.extract_index(element, names)
-            sub_feat, sub_ei, sub_names, sub_ind, sub_nt, sub_et, pos = data.comp_graph(
-                ind, n_hops, self.problem, names, node_types, edge_types, return_pos=True)
+            if ew is not None:
+                sub_feat, sub_ei, sub_names, sub_ind, sub_nt, sub_et, pos, sub_w = data.comp_graph(
+                    ind, n_hops, self.problem, names, node_types, edge_types, return_pos=True,
+                    edge_weight=ew)
+            else:
+                sub_feat, sub_ei, sub_names, sub_ind, sub_nt, sub_et, pos = data.comp_graph(
+                    ind, n_hops, self.problem, names, node_types, edge_types, return_pos=True)
             if pathways is not None:
                 sub_pw, sub_pw_names, _ = Pathways(pathways, pathway_names,
                                                    pathway_types).comp_graph(sub_names)
@@ -366,7 +396,7 @@ class Explainer:
             # writes to it, so the run reads the caller's tensors and names directly)
             sub_feat, sub_ei, sub_names = feat, ei, names
             ind = sub_ind = self.extract_index(element, sub_names)
-            sub_nt, sub_et = node_types, edge_types
+            sub_nt, sub_et, sub_w = node_types, edge_types, ew
             if pathways is not None:
                 sub_pw, sub_pw_names = pathways, pathway_names
         if "graph" not in self.problem and not self.edge_masks and (self.element_type is not None or
@@ -386,6 +416,7 @@ class Explainer:
         S = Data(sub_feat, sub_ei).element_size(self.problem)
         return {"link": link, "label_type": label_type, "sub_feat": sub_feat, "sub_ei": sub_ei,
                 "sub_names": sub_names, "sub_ind": sub_ind, "sub_nt": sub_nt, "sub_et": sub_et,
+                "sub_w": sub_w,
                 "h_ntypes": h_ntypes, "h_etypes": h_etypes, "padded_dims": padded_dims, "sub_pw": sub_pw,
                 "sub_pw_names": sub_pw_names, "sub_pw_inds": sub_pw_inds, "S": S,
                 "has_pathways": pathways is not None, "ind": ind,
@@ -496,6 +527,8 @@ class Explainer:
         clock.mark("plan")
         # typed edge problems (nn.RelLinkModel): the subgraph's edge types and the query's own
         typed = {"edge_type": c["sub_et"], "label_type": c["label_type"]} if self.edge_masks else {}
+        # weighted graphs: the computational subgraph's edge weights, for every path
+        wkw = {"edge_weight": c["sub_w"]} if c.get("sub_w") is not None else {}
 
         if cached:
             plan, verify = cached[1], None
@@ -506,8 +539,8 @@ class Explainer:
                                                        **typed)
         else:
             plan = pipeline.build_plan(self.arch, sub_feat, sub_ei, [sub_ind], *geo,
-                                       module_state=mstate, attention=self.attention_engine)
-            verify = lambda: pipeline.verify_plan(plan, self.arch, sub_feat, sub_ei, sub_ind, *geo)
+                                       module_state=mstate, attention=self.attention_engine, **wkw)
+            verify = lambda: pipeline.verify_plan(plan, self.arch, sub_feat, sub_ei, sub_ind, *geo, **wkw)
         clock.mark("verify")
         arch_check = "off"
         mode = self.params.get("verify_arch", True)
@@ -517,7 +550,7 @@ class Explainer:
                 cached = None  # checked again below
         if plan is not None and mode and not cached:
             if verify is None:
-                verify = lambda: pipeline.verify_plan(plan, self.arch, sub_feat, sub_ei, sub_ind, *geo) \
+                verify = lambda: pipeline.verify_plan(plan, self.arch, sub_feat, sub_ei, sub_ind, *geo, **wkw) \
                     if not self.edge_masks else pipeline.verify_edge_plan(plan, self.arch, sub_feat, sub_ei,
                                                                           *c["link"], **typed)
             # the check guards the arch lowering (program.compile_arch + the plan's term
@@ -581,7 +614,7 @@ class Explainer:
                 ys = [pipeline.generic_outputs(
                     self.arch, sub_feat, sub_ei,
                     engine.unpack_masks(bits[i], S) if masks[i] is None else masks[i],
-                    sub_ind, self.problem, *geo, batch=batch, q4=q4) for i in range(t0, t1)]
+                    sub_ind, self.problem, *geo, batch=batch, q4=q4, **wkw) for i in range(t0, t1)]
                 return torch.stack(ys) if ys else torch.empty((0, R), device=device)
             y = sharding.gather_map(times, generic, g)
 
@@ -683,12 +716,13 @@ class Explainer:
         geo = (c["sub_nt"], c["sub_et"], c["h_ntypes"], c["h_etypes"], c["padded_dims"])
         Q = len(inds)
         assert len(set(inds)) == Q, "run_queries: duplicate query elements"
+        wkw = {"edge_weight": c["sub_w"]} if c.get("sub_w") is not None else {}
         plan = pipeline.build_plan(self.arch, sub_feat, sub_ei, inds, *geo, module_state=mstate,
-                                   attention=self.attention_engine)
+                                   attention=self.attention_engine, **wkw)
         assert plan is not None and not getattr(plan, "multi_type", False), \
             "run_queries needs an engine-compilable single-node-type architecture"
         if self.params.get("verify_arch", True):
-            ok, err = pipeline.verify_plan(plan, self.arch, sub_feat, sub_ei, inds, *geo)
+            ok, err = pipeline.verify_plan(plan, self.arch, sub_feat, sub_ei, inds, *geo, **wkw)
             assert ok, f"compiled arch disagrees with its torch forward (max err {err:.3g})"
         sampler = self.params.get("mask_sampler", "compat")
         _, epochs = Mask.assertions_mask_generator(self.params)

@@ -24,18 +24,23 @@ class Model:
             hops //= num_relations
         return hops
 
-    def infer(self, feat, edge_index, node_types=None, edge_types=None, batch=None):
+    def infer(self, feat, edge_index, node_types=None, edge_types=None, batch=None, edge_weight=None):
         """model.py:62-116 — call convention picked from the forward signature.  A forward of
         three parameters is a graph-level (pooled) model, called `arch(x, edge_index, batch)`:
         `batch` [n] gives each node's graph (the copy of the union graph it belongs to; None: one
-        graph).  An edge-level model's (x, edge_index, edge_label_index) is not that form."""
-        names = list(inspect.signature(self.arch.forward).parameters)
+        graph).  An edge-level model's (x, edge_index, edge_label_index) is not that form.
+        `edge_weight` ([E], one per edge of `edge_index`) is passed on as that keyword."""
+        names = [n for n in inspect.signature(self.arch.forward).parameters if n != "edge_weight"]
         nargs = len(names)
+        # the optional trailing edge_weight keyword is no part of the call convention
+        kw = {} if edge_weight is None else {"edge_weight": edge_weight}
         with torch.no_grad():
             if nargs == 2:
-                return self.arch(feat, edge_index)
+                return self.arch(feat, edge_index, **kw)
             if nargs == 3 and names[2] != "edge_label_index":
-                return self.arch(feat, edge_index, batch)
+                return self.arch(feat, edge_index, batch, **kw)
+            if edge_weight is not None:
+                raise TypeError("edge_weight with the 4-argument (typed) call is not supported")
             if nargs == 4 and node_types is not None and edge_types is not None:
                 return self.arch(feat, edge_index, node_types, edge_types)
         raise TypeError("arch.forward must take (x, edge_index), (x, edge_index, batch) or "

@@ -83,7 +83,11 @@ class Linear(nn.Module):
 
 class GCNConv(MessagePassing):
     """GCNConv(normalize=True, add_self_loops=True): D^-1/2 (A + I) D^-1/2 X W^T + b, where
-    existing self-loops are replaced by one weight-1 loop per node."""
+    existing self-loops are replaced by one weight-1 loop per node.  With an `edge_weight` (one
+    weight >= 0 per edge) A holds the weights and a node that has self-loops keeps, instead of the
+    weight-1 loop, one loop of its LAST self-loop's weight (gcn_norm's add_remaining_self_loops
+    with fill_value 1); "last" is taken from the edge position, so the result does not depend on
+    how a duplicate-index assignment is ordered on the device."""
 
     def __init__(self, in_channels, out_channels, bias=True, improved=False, cached=False,
                  add_self_loops=True, normalize=True, **kwargs):
@@ -96,7 +100,9 @@ class GCNConv(MessagePassing):
         self.lin = Linear(in_channels, out_channels, bias=False, weight_initializer="glorot")
         self.bias = nn.Parameter(torch.zeros(out_channels)) if bias else None
 
-    def forward(self, x, edge_index):
+    def forward(self, x, edge_index, edge_weight=None):
+        if edge_weight is not None:
+            return self._forward_weighted(x, edge_index, edge_weight)
         n = x.size(0)
         ei = edge_index.long()
         keep = ei[0] != ei[1]
@@ -113,6 +119,36 @@ class GCNConv(MessagePassing):
             out = out + self.bias
         return out
 
+    def _forward_weighted(self, x, edge_index, edge_weight):
+        n = x.size(0)
+        ei = edge_index.long()
+        w = edge_weight.reshape(-1).to(x.dtype)
+        keep = ei[0] != ei[1]
+        # loop weight: the last self-loop of each node by edge position, 1 for a node without one.
+        # The loops (ascending positions) are grouped by node with a stable sort; the last entry of
+        # each group is written, so no index is assigned twice
+        loops = torch.nonzero(~keep).reshape(-1)
+        lw = torch.ones(n, dtype=x.dtype, device=x.device)
+        if loops.numel():
+            order = torch.argsort(ei[0][loops], stable=True)
+            ns, pos = ei[0][loops][order], loops[order]
+            is_last = torch.ones_like(ns, dtype=torch.bool)
+            is_last[:-1] = ns[:-1] != ns[1:]
+            lw[ns[is_last]] = w[pos[is_last]]
+        ar = torch.arange(n, device=x.device)
+        src, dst = torch.cat([ei[0][keep], ar]), torch.cat([ei[1][keep], ar])
+        ew = torch.cat([w[keep], lw])
+        deg = torch.zeros(n, dtype=x.dtype, device=x.device)
+        deg.index_add_(0, dst, ew)
+        dis = deg.pow(-0.5)
+        dis.masked_fill_(torch.isinf(dis), 0)
+        xw = self.lin(x)
+        out = torch.zeros_like(xw)
+        out.index_add_(0, dst, (dis[src] * ew * dis[dst]).unsqueeze(1) * xw[src])
+        if self.bias is not None:
+            out = out + self.bias
+        return out
+
     def extra_repr(self):
         return f"{self.in_channels}, {self.out_channels}"
 
@@ -120,20 +156,23 @@ class GCNConv(MessagePassing):
 _AGGRS = {"mean": "mean", "add": "sum", "sum": "sum", "max": "max"}
 
 
-def aggregate(xs, edge_index, n, aggr):
+def aggregate(xs, edge_index, n, aggr, edge_weight=None):
     """[n, F]: per target the mean / sum / max of the source rows xs[edge_index[0]] over its
     in-edges (duplicates as separate entries), 0 for a target without edges — the scatter-based
     aggregation of PyG 2.0.4's MessagePassing (torch_scatter fills empty segments with 0, also
-    for max, where a non-empty segment of negative rows keeps its negative maximum)."""
+    for max, where a non-empty segment of negative rows keeps its negative maximum).
+    `edge_weight` [E]: the messages are w_e * x_j (GraphConv's); the mean still divides by the
+    COUNT of in-edges."""
     ei = edge_index.long()
     src, dst = ei[0], ei[1]
     kind = _AGGRS[aggr]
+    msg = xs[src] if edge_weight is None else edge_weight.reshape(-1, 1).to(xs.dtype) * xs[src]
     if kind == "max":
         idx = dst.unsqueeze(1).expand(-1, xs.size(1))
         return torch.zeros((n, xs.size(1)), dtype=xs.dtype, device=xs.device).scatter_reduce(
-            0, idx, xs[src], reduce="amax", include_self=False)
+            0, idx, msg, reduce="amax", include_self=False)
     s = torch.zeros((n, xs.size(1)), dtype=xs.dtype, device=xs.device)
-    s.index_add_(0, dst, xs[src])
+    s.index_add_(0, dst, msg)
     if kind == "sum":
         return s
     cnt = torch.zeros(n, dtype=xs.dtype, device=xs.device)
@@ -167,9 +206,10 @@ class SAGEConv(MessagePassing):
 
 
 class GraphConv(MessagePassing):
-    """GraphConv (PyG 2.0.4, no edge_weight): lin_rel(aggr_j x_j) + lin_root(x) with `aggr` in
-    add (= sum) / mean / max; lin_rel carries the bias, lin_root has none.  Tuple inputs
-    (x_src, x_dst) for bipartite relations."""
+    """GraphConv (PyG 2.0.4): lin_rel(aggr_j w_ji x_j) + lin_root(x) with `aggr` in add (= sum) /
+    mean / max and w_ji the optional `edge_weight` (1 without one; any finite value, self-loops
+    are ordinary edges); lin_rel carries the bias, lin_root has none.  Tuple inputs (x_src, x_dst)
+    for bipartite relations."""
 
     def __init__(self, in_channels, out_channels, aggr="add", bias=True, **kwargs):
         super().__init__()
@@ -181,9 +221,9 @@ class GraphConv(MessagePassing):
         self.lin_rel = Linear(in_channels[0], out_channels, bias=bias)
         self.lin_root = Linear(in_channels[1], out_channels, bias=False)
 
-    def forward(self, x, edge_index):
+    def forward(self, x, edge_index, edge_weight=None):
         xs, xd = (x, x) if isinstance(x, torch.Tensor) else x
-        return self.lin_rel(aggregate(xs, edge_index, xd.size(0), self.aggr)) + self.lin_root(xd)
+        return self.lin_rel(aggregate(xs, edge_index, xd.size(0), self.aggr, edge_weight)) + self.lin_root(xd)
 
     def extra_repr(self):
         return f"{self.in_channels}, {self.out_channels}, aggr={self.aggr}"
@@ -509,10 +549,10 @@ class ConvStack(nn.Module):
                        else nn.ReLU())
         self.fc = nn.ModuleList(fcs)
 
-    def forward(self, x, edge_index):
+    def forward(self, x, edge_index, edge_weight=None):
         for i, c in enumerate(self.conv):
             if i % 2 == 0:
-                x = c(x, edge_index)
+                x = c(x, edge_index) if edge_weight is None else c(x, edge_index, edge_weight=edge_weight)
             elif isinstance(x, dict):
                 x = {k: c(v) for k, v in x.items()}
             else:
@@ -597,10 +637,11 @@ class BlockStack(nn.Module):
                        else nn.ReLU())
         self.fc = nn.ModuleList(fcs)
 
-    def forward(self, x, edge_index):
+    def forward(self, x, edge_index, edge_weight=None):
         n = self.block_len
         for i in range(0, len(self.conv), n):
-            z = self.conv[i](x, edge_index)
+            z = self.conv[i](x, edge_index) if edge_weight is None else \
+                self.conv[i](x, edge_index, edge_weight=edge_weight)
             for m in self.conv[i + 1:i + n]:
                 z = m(z)
             x = z + x if self.residual and z.shape[-1] == x.shape[-1] else z
@@ -833,8 +874,9 @@ class PooledModel(nn.Module):
                        else nn.ReLU())
         self.fc = nn.ModuleList(fcs)
 
-    def forward(self, x, edge_index, batch=None):
-        h = self.encoder(x, edge_index)
+    def forward(self, x, edge_index, batch=None, edge_weight=None):
+        h = self.encoder(x, edge_index) if edge_weight is None else \
+            self.encoder(x, edge_index, edge_weight=edge_weight)
         h = global_pool(h, batch, self.pool)
         for layer in self.fc:
             h = layer(h)

@@ -70,7 +70,7 @@ def clear_programs():
 
 
 def compiled_program(arch, edge_type_names=None, node_type_names=None, state=None,
-                     attention=False):
+                     attention=False, edge_weight=False):
     """compile_arch(arch, ...) once per module state: keyed by the module (identity, checked by
     weak reference), every parameter and buffer (storage + in-place version counter: an
     optimizer step, load_state_dict or a replaced tensor compiles again) and the type names.
@@ -85,12 +85,14 @@ def compiled_program(arch, edge_type_names=None, node_type_names=None, state=Non
                  tuple((t.data_ptr(), t._version) for t in arch.buffers()))
     key = (id(arch), state,
            tuple(tuple(e) for e in edge_type_names) if edge_type_names is not None else None,
-           tuple(node_type_names) if node_type_names is not None else None, bool(attention))
+           tuple(node_type_names) if node_type_names is not None else None, bool(attention),
+           bool(edge_weight))
     hit = _PROGRAMS.get(key)
     if hit is not None and hit[0]() is arch:
         _PROGRAMS.move_to_end(key)
         return hit[1]
-    prog = compile_arch(arch, edge_type_names, node_type_names, attention=bool(attention))
+    prog = compile_arch(arch, edge_type_names, node_type_names, attention=bool(attention),
+                        edge_weight=bool(edge_weight))
     _PROGRAMS[key] = (weakref.ref(arch), prog)
     while len(_PROGRAMS) > 8:
         _PROGRAMS.popitem(last=False)
@@ -99,7 +101,7 @@ def compiled_program(arch, edge_type_names=None, node_type_names=None, state=Non
 
 def build_plan(arch, feat, edge_index, queries, node_type=None, edge_type=None,
                node_type_names=None, edge_type_names=None, padded_dims=None, module_state=None,
-               attention=False):
+               attention=False, edge_weight=None):
     """ForwardPlan for `arch` on the (sub)graph, or None when the engine cannot run it.
     `attention=True` (opt-in, Explainer params["attention_engine"]) also compiles GATConv
     relations, which otherwise run on the generic torch path.
@@ -112,14 +114,24 @@ def build_plan(arch, feat, edge_index, queries, node_type=None, edge_type=None,
     node type and the query is the reference's `out[sub_ind, 0]` — row sub_ind of the output
     node type's block — so `queries` are positions inside that type and are mapped to subgraph
     nodes here.  The plan is marked `multi_type` (its per-row outputs then go through
-    `multi_type_targets`)."""
+    `multi_type_targets`).
+
+    `edge_weight` ([E], one per edge of `edge_index`; homogeneous graphs): the arch is compiled
+    for a weighted graph (GCNConv / GraphConv only) and the plan carries the weights.  A weight
+    vector that is itself invalid (wrong length, not finite, negative with a GCNConv) raises
+    ValueError: no path could run it."""
     multi = node_type_names is not None and node_type is not None and \
         len(torch.unique(node_type)) >= 2
     hetero = edge_type_names is not None and edge_type is not None
+    if edge_weight is not None:
+        require_edge_weight_arch(arch)
+        if multi or hetero or node_type is not None or edge_type is not None:
+            raise NotImplementedError("edge_weight on a heterogeneous (typed) graph is not supported")
+        edge_weight = checked_edge_weight(arch, edge_weight, edge_index.shape[1])
     try:
         prog = compiled_program(arch, edge_type_names if hetero else None,
                                 node_type_names if multi else None, module_state,
-                                attention=attention)
+                                attention=attention, edge_weight=edge_weight is not None)
         check_rel_features(prog, feat)
     except UnsupportedArch as e:
         warnings.warn(f"engine cannot compile arch ({e}); using the generic torch path")
@@ -150,7 +162,7 @@ def build_plan(arch, feat, edge_index, queries, node_type=None, edge_type=None,
         else:
             rels = relation_edges(edge_index, edge_type if hetero else None,
                                   len(edge_type_names) if hetero else 1)
-        plan = engine.ForwardPlan(prog, x, rels, queries, node_type=nt)
+        plan = engine.ForwardPlan(prog, x, rels, queries, node_type=nt, edge_weight=edge_weight)
     except ValueError as e:
         warnings.warn(f"engine plan rejected ({e}); using the generic torch path")
         return None
@@ -289,31 +301,59 @@ def multi_type_targets(y_rows, empty, batch, sub_ind, S, q4=True):
 
 def pooled_call(arch):
     """True for a graph-level model: a forward of three parameters (x, edge_index, batch), the
-    form Model.infer calls with the union graph's copy index per node (nn.PooledModel)."""
+    form Model.infer calls with the union graph's copy index per node (nn.PooledModel).  An
+    optional `edge_weight` keyword is no part of the form."""
     forward = getattr(arch, "forward", None)
     if forward is None:
         return False
     try:
-        names = list(inspect.signature(forward).parameters)
+        names = [n for n in inspect.signature(forward).parameters if n != "edge_weight"]
     except (TypeError, ValueError):
         return False
     return len(names) == 3 and names[2] != "edge_label_index"
 
 
+def checked_edge_weight(arch, edge_weight, n_edges):
+    """The validated host copy (float32 numpy [n_edges]) of a weight vector for `arch`: one finite
+    weight per edge, none negative when the arch holds a GCNConv (matched by class name, as
+    program.compile_arch matches it).  ValueError otherwise: no path could run such weights."""
+    gcn = any(type(m).__name__ == "GCNConv" for m in arch.modules())
+    return engine.check_edge_weight(edge_weight, n_edges, gcn)
+
+
+def require_edge_weight_arch(arch):
+    """TypeError unless `arch.forward` has an `edge_weight` parameter (or takes **kwargs): the
+    weighted paths call arch(x, edge_index[, batch], edge_weight=w)."""
+    try:
+        ps = inspect.signature(arch.forward).parameters
+    except (TypeError, ValueError, AttributeError):
+        raise TypeError("edge_weight given, but arch.forward has no readable signature")
+    if "edge_weight" not in ps and not any(p.kind == p.VAR_KEYWORD for p in ps.values()):
+        raise TypeError(f"edge_weight given, but {type(arch).__name__}.forward has no edge_weight "
+                        "parameter: the model cannot be called on a weighted graph")
+
+
 def generic_outputs(arch, feat, edge_index, mask, element_index, problem, node_type=None,
                     edge_type=None, node_type_names=None, edge_type_names=None,
-                    padded_dims=None, batch=None, q4=True):
+                    padded_dims=None, batch=None, q4=True, edge_weight=None):
     """wlm.py:349-436 semantics per batch of mask rows with the user's module in torch.
     Returns y [R] (the regression target of each row; for multi-node-type graphs the
     reference's output[ind::S] collapse, quirk Q4, broadcast over its batch).  A list of
     element indices (single-node-type graphs) returns y [R, Q]: every query's extraction from
-    the same union-graph forward."""
+    the same union-graph forward.  `edge_weight` ([E], homogeneous graphs): each copy's kept
+    edges carry their weights, `arch(x, edge_index[, batch], edge_weight=w)`."""
     pooled = pooled_call(arch)
+    if edge_weight is not None:
+        require_edge_weight_arch(arch)
+        if node_type is not None or edge_type is not None:
+            raise NotImplementedError("edge_weight on a heterogeneous (typed) graph is not supported")
+        edge_weight = edge_weight.reshape(-1).to(device=mask.device, dtype=torch.float32)
     if isinstance(element_index, (list, tuple)):
         if pooled:
             raise ValueError("a pooled (graph-level) model has one output per graph: no query list")
         return _generic_multi(arch, feat, edge_index, mask, element_index, problem, node_type,
-                              edge_type, node_type_names, edge_type_names, padded_dims, batch)
+                              edge_type, node_type_names, edge_type_names, padded_dims, batch,
+                              edge_weight)
     data = Data(feat, edge_index)
     mc = Model(arch)
     R, S = mask.shape
@@ -322,7 +362,11 @@ def generic_outputs(arch, feat, edge_index, mask, element_index, problem, node_t
     for r0 in range(0, R, batch):
         mb = mask[r0:r0 + batch]
         B = mb.shape[0]
-        cf, cnt, pei, pet = data.perturbator(mb, problem, node_type, edge_type)
+        pew = None
+        if edge_weight is not None:
+            cf, cnt, pei, pet, pew = data.perturbator(mb, problem, node_type, edge_type, edge_weight)
+        else:
+            cf, cnt, pei, pet = data.perturbator(mb, problem, node_type, edge_type)
         pei = pei.long()
         n_types = 1 if node_type_names is None else len(torch.unique(node_type))
         if node_type is not None and edge_type is not None and node_type_names is not None \
@@ -334,13 +378,13 @@ def generic_outputs(arch, feat, edge_index, mask, element_index, problem, node_t
             # removed), one output row per copy; column out_col (0) is the regression target
             # (cf is a dict for a single-node-type graph with type names: the device is the mask's)
             gb = torch.arange(B, device=mb.device).repeat_interleave(S)
-            out = mc.infer(cf, pei, batch=gb)
+            out = mc.infer(cf, pei, batch=gb, edge_weight=pew)
             if out.dim() != 2 or out.shape[0] != B:
                 raise RuntimeError(f"a pooled model must return [{B}, out], got {tuple(out.shape)}")
             ys.append(out[:, 0].reshape(-1).float())
             continue
         if n_types < 2:
-            out = mc.infer(cf, pei, cnt, pet)
+            out = mc.infer(cf, pei, cnt, pet, edge_weight=pew)
         else:
             # one arch call over the disjoint union per node type (§8f2); HETERO_BATCHED =
             # False restores the reference's per-copy loop
@@ -369,7 +413,7 @@ def generic_outputs(arch, feat, edge_index, mask, element_index, problem, node_t
 
 
 def _generic_multi(arch, feat, edge_index, mask, queries, problem, node_type, edge_type,
-                   node_type_names, edge_type_names, padded_dims, batch):
+                   node_type_names, edge_type_names, padded_dims, batch, edge_weight=None):
     """generic_outputs for several queries of a single-node-type graph: [R, Q]."""
     data = Data(feat, edge_index)
     mc = Model(arch)
@@ -379,13 +423,17 @@ def _generic_multi(arch, feat, edge_index, mask, queries, problem, node_type, ed
     for r0 in range(0, R, batch):
         mb = mask[r0:r0 + batch]
         B = mb.shape[0]
-        cf, cnt, pei, pet = data.perturbator(mb, problem, node_type, edge_type)
+        pew = None
+        if edge_weight is not None:
+            cf, cnt, pei, pet, pew = data.perturbator(mb, problem, node_type, edge_type, edge_weight)
+        else:
+            cf, cnt, pei, pet = data.perturbator(mb, problem, node_type, edge_type)
         pei = pei.long()
         if node_type is not None and edge_type is not None and node_type_names is not None \
                 and edge_type_names is not None:
             cf = data.homo2hetero(cf, cnt, node_type_names, padded_dims)
             pei = data.homo2hetero(pei, pet, edge_type_names)
-        out = mc.infer(cf, pei, cnt, pet)
+        out = mc.infer(cf, pei, cnt, pet, edge_weight=pew)
         if isinstance(out, dict):
             out, _ = mc.hetero2homo_output(out)
         ys.append(torch.stack([mc.extract_node_edge_output(out, int(q), S).reshape(-1).float()
@@ -394,7 +442,8 @@ def _generic_multi(arch, feat, edge_index, mask, queries, problem, node_type, ed
 
 
 def verify_plan(plan, arch, feat, edge_index, query, node_type=None, edge_type=None,
-                node_type_names=None, edge_type_names=None, padded_dims=None, rows=8, tol=1e-4):
+                node_type_names=None, edge_type_names=None, padded_dims=None, rows=8, tol=1e-4,
+                edge_weight=None):
     """Check the compiled program against the user's module on a few random masks (guards the
     registration-order lowering in program.compile_arch).  `query` may be the list of a
     multi-query plan's queries: every output column is then checked."""
@@ -406,12 +455,14 @@ def verify_plan(plan, arch, feat, edge_index, query, node_type=None, edge_type=N
     if isinstance(query, (list, tuple)):
         assert not multi, "multi-query plans are single-node-type"
         ref = generic_outputs(arch, feat, edge_index, mask, list(query), "node", node_type,
-                              edge_type, node_type_names, edge_type_names, padded_dims)
+                              edge_type, node_type_names, edge_type_names, padded_dims,
+                              edge_weight=edge_weight)
         got = plan.forward(engine.pack_masks(mask))[:, :len(query)]
         err = (ref - got).abs().max().item()
         return err <= tol * max(1.0, ref.abs().max().item()), err
     ref = generic_outputs(arch, feat, edge_index, mask, query, "node", node_type, edge_type,
-                          node_type_names, edge_type_names, padded_dims, q4=not multi)
+                          node_type_names, edge_type_names, padded_dims, q4=not multi,
+                          edge_weight=edge_weight)
     bits = engine.pack_masks(mask)
     got = plan.forward(bits)[:, 0]
     if multi:  # per-copy outputs on both sides (zero for copies without edges)

@@ -118,6 +118,9 @@ class ModelProgram:
     # PooledModel: the convs are its encoder's, the head its `fc`; between them each graph's node
     # rows reduce to one row ("mean" | "sum" | "max"), and the program has one output per graph
     pool: Optional[str] = None
+    # compiled for a weighted graph (compile_arch(edge_weight=True)): every conv is a GCNConv or a
+    # GraphConv, the two convs of PyG 2.0.4 that take an edge_weight; the plan then needs the weights
+    weighted: bool = False
 
     @property
     def hops(self):
@@ -693,7 +696,7 @@ def _check_widths(prog):
 POOL_KIND = {"mean": "mean", "add": "sum", "sum": "sum", "max": "max"}
 
 
-def _compile_pooled(arch, edge_type_names, node_type_names, attention):
+def _compile_pooled(arch, edge_type_names, node_type_names, attention, edge_weight=False):
     """nn.PooledModel (matched by class name + `encoder`, `pool`, `fc`): the encoder's conv
     layers, the readout, then the Linear / activation units of `fc` as the head."""
     pool = arch.pool
@@ -701,7 +704,7 @@ def _compile_pooled(arch, edge_type_names, node_type_names, attention):
         raise UnsupportedArch(f"PooledModel(pool={pool!r})")
     if node_type_names is not None and len(node_type_names) >= 2:
         raise UnsupportedArch("PooledModel on a multi-node-type graph")
-    prog = compile_arch(arch.encoder, edge_type_names, node_type_names, attention)
+    prog = compile_arch(arch.encoder, edge_type_names, node_type_names, attention, edge_weight)
     if prog.link_act is not None:
         raise UnsupportedArch("PooledModel over an edge-level (link) encoder")
     if prog.pool is not None:
@@ -724,12 +727,20 @@ def _compile_pooled(arch, edge_type_names, node_type_names, attention):
 
 
 def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
-                 attention=False) -> ModelProgram:
+                 attention=False, edge_weight=False) -> ModelProgram:
     """Lower `arch` to a ModelProgram.  `edge_type_names` (list of (src, rel, dst) tuples in
     homogenised edge-type order, data.py:743-822) enables HeteroConv relations;
     `node_type_names` with two or more types selects the multi-node-type lowering.
     `attention=True` (opt-in) also lowers GATConv relations, to "att" terms, and GATv2Conv
-    relations, to "att2" terms; by default an arch with either raises UnsupportedArch."""
+    relations, to "att2" terms; by default an arch with either raises UnsupportedArch.
+    `edge_weight=True`: the arch will be called with an edge_weight.  Only GCNConv and GraphConv take
+    one in PyG 2.0.4, so every conv must be one of the two (inside a ConvStack, a BlockStack or a
+    PooledModel encoder alike); the program is marked `weighted`."""
+    if edge_weight:
+        if type(arch).__name__ in ("LinkModel", "RelLinkModel"):
+            raise UnsupportedArch("edge_weight with an edge-level (link) model")
+        if edge_type_names is not None or node_type_names is not None:
+            raise UnsupportedArch("edge_weight on a heterogeneous (typed) graph")
     if type(arch).__name__ == "LinkModel" and hasattr(arch, "encoder"):
         prog = compile_arch(arch.encoder, edge_type_names, node_type_names, attention)
         if prog.pool is not None:
@@ -753,7 +764,7 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
             prog.link_rel = _f32(emb)
         return prog
     if type(arch).__name__ == "PooledModel" and all(hasattr(arch, a) for a in ("encoder", "pool", "fc")):
-        return _compile_pooled(arch, edge_type_names, node_type_names, attention)
+        return _compile_pooled(arch, edge_type_names, node_type_names, attention, edge_weight)
     rel_index = None
     if edge_type_names is not None:
         rel_index = {tuple(et): i for i, et in enumerate(edge_type_names)}
@@ -766,6 +777,9 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
         prog.n_types = len(node_type_names)
     i = 0
     while i < len(units) and _is_conv(units[i], attention):
+        if edge_weight and not (type(units[i]).__name__ == "GCNConv" or _is_graphconv(units[i])):
+            raise UnsupportedArch(f"{type(units[i]).__name__} takes no edge_weight (GCNConv and "
+                                  "GraphConv do)")
         if multi:
             terms, bias, f_in, f_out, prog.out_type = _conv_layer_multi(
                 units[i], rel_index, list(node_type_names), attention)
@@ -809,6 +823,7 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
     _check_widths(prog)
     if type(arch).__name__ == "BlockStack" and getattr(arch, "residual", False):
         _add_residuals(prog)
+    prog.weighted = bool(edge_weight)
     return prog
 
 

@@ -40,7 +40,9 @@
  *                                        (v27 addendum, no version change: xpg_layer_desc.pool
  *                                        appended; a conv stack followed by a global mean / add /
  *                                        max readout and a dense head, one output per mask row;
- *                                        XPG_TERM_ATT2 = 7: GATv2Conv layers, enum xpg_term below)
+ *                                        XPG_TERM_ATT2 = 7: GATv2Conv layers, enum xpg_term below;
+ *                                        xpg_masked_forward_w: the same with PyG's edge_weight of
+ *                                        GCNConv / GraphConv, struct xpg_edge_weights below)
  *   xpg_pool_rows / _workspace / _describe — the readout alone (PyG global_mean_pool /
  *                                        global_add_pool / global_max_pool over one graph per row)
  *   xpg_forward_describe / xpg_wide_variants — none: host queries of xpg_masked_forward's own
@@ -533,6 +535,55 @@ int xpg_post_rows(float* h, int64_t M, int64_t ld, int64_t f_out, const xpg_post
  * A HOST function sharing the launcher's selection; XPG_ENOSPC when `nbytes` do not hold the text. */
 int xpg_post_describe(int64_t M, int64_t ld, int64_t f_out, const xpg_post_desc* post, char* buf,
                       size_t nbytes);
+
+/* Edge weights (v27 addendum: new symbols only; the version, every struct above and every entry
+ * point above are unchanged).  One finite float per edge of the graph (PyG 2.0.4's `edge_weight` of
+ * GCNConv and GraphConv), handed beside the plan already gathered into the plan's CSR orders, all
+ * device arrays.  weights == NULL: each _w entry point is its _post namesake, same results (the
+ * _post entry points are that case of the same code).  Node masks as ever: in mask row b an edge
+ * (u -> t) of weight w_e survives iff bit(b, u) & bit(b, t); a self-loop is an edge like any other.
+ *   GCN term (gcn_norm with add_remaining_self_loops(fill_value = 1); weights >= 0):
+ *     lw[v]  = loop_w[v] when v is kept, else 1   (loop_w: the weight of v's LAST self-loop in edge
+ *              order, 1 for a node without one)
+ *     deg[v] = lw[v] + sum of w_e over v's kept non-loop in-edges, fp32, in CSR order
+ *     dis[v] = deg[v] > 0 ? 1 / sqrt(deg[v]) : 0
+ *     out[t] = dis[t]^2 lw[t] x[t] + sum over kept (u -> t) of dis[u] w_e dis[t] x[u]
+ *   SUM term: self_sum[t] x[t] + sum over kept in-edges of w_e x[u] (nothing for a masked-out t).
+ *   MEAN term: that sum divided by the COUNT of kept in-edges, self_mult[t] included, at least 1.
+ *   MAX term: the element-wise maximum of w_e x[u] over the kept in-edges and, with self_mult[t] > 0,
+ *     of the self-loops, folded per element as x[t] >= 0 ? self_wmax[t] x[t] : self_wmin[t] x[t];
+ *     an empty set gives 0.  Any finite weight, negative ones included, for SUM / MEAN / MAX.
+ *   ROOT terms, the table / raw forms of layer 1, post-ops, the pooled readout and the head are
+ *   unchanged (they run around the aggregation).
+ * k_degree_w writes the in-edge counts as k_degree does (-1 for a masked-out node) and, for plans
+ * with a GCN term, the weighted degrees (1 for a masked-out node); k_agg_w<L1, LPS, NV> is k_agg's
+ * item / lane mapping with the per-edge weight loaded beside each in-edge.
+ * Host checks, XPG_EINVAL before any launch: edge_masks or edge_dot; n_rel > 1; tgt_type
+ * (multi-node-type plans); a term kind other than GCN / MEAN / ROOT / SUM / MAX; a missing array
+ * (layers, agg_w, self_sum, self_wmax, self_wmin; deg_w and loop_w with a GCN term).  A weighted
+ * plan runs on the multi-kernel path only (a forced rows / fused / wide path under
+ * XPG_FORWARD_STRICT=1 is refused).  xpg_forward_describe_w writes
+ * `unfused weights=k_degree_w+k_agg_w`, then the ` post<l>=...` tokens.  The workspace is that of
+ * the same plan without weights on the multi-kernel path plus, at its end and only with a GCN
+ * term, the weighted degrees (rows * n0 floats, rounded up to 256 bytes). */
+typedef struct xpg_layer_weights {
+  const float* agg_w;      /* [n_edges] weight of in-edge e (the index of agg_src / agg_f0)   */
+  const float* self_sum;   /* [n_rel * n_tgt] sum of the weights of the target's self-loops  */
+  const float* self_wmax;  /* [n_rel * n_tgt] their maximum (unread where self_mult == 0)    */
+  const float* self_wmin;  /* [n_rel * n_tgt] their minimum                                  */
+} xpg_layer_weights;
+typedef struct xpg_edge_weights {
+  const float* deg_w;      /* [n_deg_edges] weight of each deg_src entry (GCN terms)         */
+  const float* loop_w;     /* [n_rel * n0] last self-loop weight of each F_0 node, else 1    */
+  const xpg_layer_weights* layers; /* host array [n_layers]                                  */
+} xpg_edge_weights;
+int xpg_forward_workspace_w(const xpg_forward_plan* plan, const xpg_post_desc* post,
+                            const xpg_edge_weights* weights, int64_t rows, size_t* bytes);
+int xpg_masked_forward_w(const xpg_forward_plan* plan, const xpg_post_desc* post,
+                         const xpg_edge_weights* weights, const uint32_t* bits, int64_t rows, float* y,
+                         void* workspace, size_t workspace_bytes, xpg_stream_t stream);
+int xpg_forward_describe_w(const xpg_forward_plan* plan, const xpg_post_desc* post,
+                           const xpg_edge_weights* weights, int64_t rows, char* buf, size_t n);
 
 /* Optional per-kernel timing of xpg_masked_forward's wide (full-graph) path (v13): with profiling
  * on, every launch of a profiled kernel is bracketed by two hipEvents on its stream;

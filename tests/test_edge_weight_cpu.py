@@ -1,0 +1,380 @@
+"""Weighted graphs (edge_weight for GCNConv / GraphConv), the parts that need no GPU: the nn.py
+modules against the fp64 restatement of tests/edge_weight_ref.py, the lowering flag, the plan's
+weight arrays against a brute-force loop, the C-ABI's host checks and describe texts on synthetic
+descriptors through the loaded library, and the Explainer's refusals."""
+import copy
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+import edge_weight_ref as ewr
+from test_aggr_cpu import make_plan as make_plan_raw
+from test_dispatch_cpu import ENV, GCN, PTR, SAGE, describe, make_plan
+
+from bikg_graph_explainability_public_amd import _lib, engine, pipeline
+from bikg_graph_explainability_public_amd import nn as xnn
+from bikg_graph_explainability_public_amd.nn import BlockStack, ConvStack, PooledModel
+from bikg_graph_explainability_public_amd.program import UnsupportedArch, compile_arch
+
+
+@pytest.fixture(autouse=True)
+def _default_path(monkeypatch):
+    for k in tuple(ENV) + ("XPG_FORWARD", "XPG_FORWARD_STRICT"):
+        monkeypatch.delenv(k, raising=False)
+
+
+# ------------------------------------------------------------------ nn.py against the restatement
+def _graph():
+    """12 nodes: duplicate edges (2 -> 3 twice, 5 -> 1 three times), node 4 with two self-loops of
+    unequal weight (0.5 then 1.75 in edge order), node 9 with one, node 11 isolated."""
+    ei = np.array([[0, 1, 2, 2, 4, 5, 5, 5, 6, 4, 7, 8, 9, 3, 10, 0, 6, 4],
+                   [1, 2, 3, 3, 4, 1, 1, 1, 0, 5, 6, 7, 9, 8, 0, 10, 4, 4]], dtype=np.int64)
+    g = np.random.default_rng(7)
+    w = g.uniform(0.25, 2.0, ei.shape[1])
+    l4 = np.nonzero((ei[0] == 4) & (ei[1] == 4))[0]
+    w[l4] = [0.5, 1.75]
+    x = g.standard_normal((12, 6))
+    return ei, w, x
+
+
+@pytest.mark.parametrize("aggr", ["gcn", "add", "mean", "max"])
+def test_weighted_modules_equal_the_restatement_in_double(aggr):
+    ei, w, x = _graph()
+    if aggr != "gcn":
+        w = w * np.where(np.arange(w.size) % 4 == 1, -1.0, 1.0)  # GraphConv: any finite weight
+    torch.manual_seed(3)
+    conv = (xnn.GCNConv(6, 5) if aggr == "gcn" else xnn.GraphConv(6, 5, aggr=aggr)).double().eval()
+    with torch.no_grad():
+        got = conv(torch.as_tensor(x), torch.as_tensor(ei), edge_weight=torch.as_tensor(w)).numpy()
+    ref = ewr.conv_rows(conv, x, ei[0], ei[1], w)
+    np.testing.assert_allclose(got, ref, rtol=0, atol=1e-12)
+    # the weights matter, and the isolated node 11 gets its own row only
+    with torch.no_grad():
+        plain = conv(torch.as_tensor(x), torch.as_tensor(ei)).numpy()
+    assert np.abs(plain - ref).max() > 1e-3
+    ones = np.ones_like(w)
+    with torch.no_grad():
+        one = conv(torch.as_tensor(x), torch.as_tensor(ei), edge_weight=torch.as_tensor(ones)).numpy()
+    if aggr == "gcn":  # the weighted gcn_norm multiplies by 1
+        np.testing.assert_allclose(one, plain, rtol=0, atol=1e-12)
+    else:
+        assert np.array_equal(one, plain)
+
+
+def test_gcn_takes_the_last_self_loop_by_edge_position():
+    """The restated loop rule equals the shim's add_remaining_self_loops, and nn.GCNConv's choice
+    follows the edge position: swapping node 4's two loop weights changes node 4's row."""
+    import importlib.util
+    import os
+    path = os.path.join(os.path.dirname(os.path.abspath(ewr.oracle.__file__)), "pyg_shim", "torch_geometric",
+                        "utils", "loop.py")
+    spec = importlib.util.spec_from_file_location("_shim_loop", path)
+    shim = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(shim)
+    add_remaining_self_loops = shim.add_remaining_self_loops
+    ei, w, x = _graph()
+    _, attr = add_remaining_self_loops(torch.as_tensor(ei), torch.as_tensor(w), 1.0, 12)
+    lw = ewr.loop_weights(ei[0], ei[1], w, 12)
+    assert np.array_equal(attr[-12:].numpy(), lw)
+    assert lw[4] == 1.75 and lw[9] == w[12] and lw[11] == 1.0
+    conv = xnn.GCNConv(6, 5).double().eval()
+    w2 = w.copy()
+    l4 = np.nonzero((ei[0] == 4) & (ei[1] == 4))[0]
+    w2[l4] = w[l4[::-1]]
+    with torch.no_grad():
+        a = conv(torch.as_tensor(x), torch.as_tensor(ei), edge_weight=torch.as_tensor(w)).numpy()
+        b = conv(torch.as_tensor(x), torch.as_tensor(ei), edge_weight=torch.as_tensor(w2)).numpy()
+    np.testing.assert_allclose(b, ewr.conv_rows(conv, x, ei[0], ei[1], w2), rtol=0, atol=1e-12)
+    assert np.abs(a[4] - b[4]).max() > 1e-3
+
+
+def test_stacks_pass_the_weights_on():
+    ei, w, x = _graph()
+    masks = np.ones((1, 12), dtype=bool)
+    for arch in (ConvStack("gcn", [6, 8, 8], [8, 1]), ewr.model("graphconv-mean", (6, 8, 8)),
+                 BlockStack("gcn", [6, 8, 8], [8, 1], norm="layer", residual=True),
+                 PooledModel(ConvStack("graphconv", [6, 8, 8], [8]), "add", [8, 1])):
+        arch = arch.double().eval()
+        got = ewr.module_outputs(arch, x, ei, w, masks, torch.float64)
+        np.testing.assert_allclose(got, ewr.union_outputs(arch, x, ei, w, masks), rtol=0, atol=1e-12)
+        assert np.abs(got - ewr.union_outputs(arch, x, ei, None, masks)).max() > 1e-4
+
+
+def test_unweighted_forward_signatures_keep_their_call_forms():
+    """The trailing edge_weight keyword is no part of the call convention: a ConvStack is still a
+    two-argument model, a PooledModel still the (x, edge_index, batch) form."""
+    assert not pipeline.pooled_call(ConvStack("gcn", [6, 8], [8, 1]))
+    assert not pipeline.pooled_call(BlockStack("gcn", [6, 8], [8, 1]))
+    assert pipeline.pooled_call(PooledModel(ConvStack("gcn", [6, 8], [8]), "mean", [8, 1]))
+
+
+# ------------------------------------------------------------------ lowering
+def test_compile_arch_marks_weighted_programs():
+    for arch in (ConvStack("gcn", [6, 8, 8], [8, 1]), ConvStack("graphconv", [6, 8, 8], [8, 1]),
+                 ConvStack("graphconv-max", [6, 8, 8], [8, 1]),
+                 BlockStack("gcn", [6, 8, 8], [8, 1], norm="layer", residual=True),
+                 PooledModel(ConvStack("graphconv", [6, 8, 8], [8]), "add", [8, 1])):
+        arch = arch.eval()
+        assert compile_arch(arch).weighted is False
+        p = compile_arch(arch, edge_weight=True)
+        assert p.weighted is True
+        assert {t.kind for c in p.convs for t in c.terms} <= set(engine.WEIGHT_KINDS)
+
+
+def test_compile_arch_refuses_convs_without_edge_weight():
+    for arch, kw in ((ConvStack("sage", [6, 8, 8], [8, 1]), {}), (ConvStack("gin", [6, 8, 8], [8, 1]), {}),
+                     (ConvStack("gat", [6, 8, 8], [8, 1]), {"attention": True}),
+                     (xnn.RGCNStack([6, 8, 8], [8, 1], 3), {}),
+                     (PooledModel(ConvStack("sage", [6, 8, 8], [8]), "mean", [8, 1]), {})):
+        compile_arch(arch.eval(), **kw)
+        with pytest.raises(UnsupportedArch, match="edge_weight"):
+            compile_arch(arch.eval(), edge_weight=True, **kw)
+    with pytest.raises(UnsupportedArch, match="link"):
+        compile_arch(xnn.LinkModel(ConvStack("gcn", [6, 8, 8], [8])).eval(), edge_weight=True)
+
+
+def test_program_cache_is_keyed_on_the_flag():
+    pipeline.clear_programs()
+    arch = ConvStack("gcn", [6, 8, 8], [8, 1]).eval()
+    a, b = pipeline.compiled_program(arch), pipeline.compiled_program(arch, edge_weight=True)
+    assert a is not b and not a.weighted and b.weighted
+    assert pipeline.compiled_program(arch) is a and pipeline.compiled_program(arch, edge_weight=True) is b
+    pipeline.clear_programs()
+
+
+# ------------------------------------------------------------------ plan arrays
+def test_weight_arrays_against_a_brute_force_loop():
+    ei, w, _ = _graph()
+    w = w.astype(np.float32)
+    E = ei.shape[1]
+    queries = [1, 4, 9]
+    arr = engine.plan_arrays(12, [ei], queries, 2, [np.arange(E, dtype=np.int64)])
+    assert engine.plan_arrays(12, [ei], queries, 2)["frontiers"][0].tolist() == arr["frontiers"][0].tolist()
+    wa = engine.weight_arrays(arr, ei[0], ei[1], w)
+    fr = arr["frontiers"]
+    # degree CSR: per F_0 node its non-loop in-edges in edge order
+    deg_w, loop_w = [], []
+    for v in fr[0]:
+        deg_w += [w[e] for e in range(E) if ei[1, e] == v and ei[0, e] != v]
+        lw = 1.0
+        for e in range(E):
+            if ei[0, e] == v and ei[1, e] == v:
+                lw = w[e]
+        loop_w.append(lw)
+    assert np.array_equal(wa["deg_w"], np.array(deg_w, np.float32))
+    assert np.array_equal(wa["loop_w"], np.array(loop_w, np.float32))
+    assert wa["loop_w"][fr[0].tolist().index(4)] == np.float32(1.75)
+    for li, lay in enumerate(wa["layers"]):
+        agg_w, ssum, smax, smin = [], [], [], []
+        for t in fr[li + 1]:
+            agg_w += [w[e] for e in range(E) if ei[1, e] == t and ei[0, e] != t]
+            loops = [w[e] for e in range(E) if ei[1, e] == t and ei[0, e] == t]
+            ssum.append(np.float32(np.sum(np.array(loops, np.float64))))
+            smax.append(max(loops) if loops else 1.0)
+            smin.append(min(loops) if loops else 1.0)
+        assert np.array_equal(lay["agg_w"], np.array(agg_w, np.float32))
+        assert np.array_equal(lay["self_sum"], np.array(ssum, np.float32))
+        assert np.array_equal(lay["self_wmax"], np.array(smax, np.float32))
+        assert np.array_equal(lay["self_wmin"], np.array(smin, np.float32))
+        assert np.array_equal(np.asarray(arr["layers"][li]["self_mult"]) > 0, lay["self_sum"] != 0)
+
+
+def test_check_edge_weight():
+    ok = engine.check_edge_weight(torch.tensor([0.5, 2.0, 0.0], dtype=torch.float64), 3, True)
+    assert ok.dtype == np.float32 and ok.tolist() == [0.5, 2.0, 0.0]
+    assert engine.check_edge_weight(torch.tensor([-1.0, 2.0]), 2, False).tolist() == [-1.0, 2.0]
+    with pytest.raises(ValueError, match="one weight per edge"):
+        engine.check_edge_weight(torch.ones(4), 3, False)
+    with pytest.raises(ValueError, match="finite"):
+        engine.check_edge_weight(torch.tensor([1.0, float("nan")]), 2, False)
+    with pytest.raises(ValueError, match="finite"):
+        engine.check_edge_weight(torch.tensor([1.0, float("inf")]), 2, False)
+    with pytest.raises(ValueError, match=">= 0"):
+        engine.check_edge_weight(torch.tensor([-1.0, 2.0]), 2, True)
+    with pytest.raises(ValueError, match="floating"):
+        engine.check_edge_weight(torch.tensor([1, 2]), 2, False)
+
+
+# ------------------------------------------------------------------ C-ABI
+def test_abi_is_additive():
+    lib = _lib.load()
+    for name in ("xpg_forward_workspace_w", "xpg_masked_forward_w", "xpg_forward_describe_w"):
+        assert name in _lib.EXPORTED and hasattr(lib, name)
+    assert _lib.ABI_VERSION == 27 and lib.xpg_abi_version() == 27
+    assert ctypes.sizeof(_lib.LayerWeights) == 32 and ctypes.sizeof(_lib.EdgeWeights) == 24
+    assert ctypes.sizeof(_lib.PostDesc) == 48
+    assert [f[0] for f in _lib.LayerDesc._fields_[-2:]] == ["seg_rel", "pool"]
+    assert _lib.ForwardPlanDesc._fields_[-1][0] == "dot_scale"
+
+
+def _weights(n, gcn=True, **missing):
+    LW = (_lib.LayerWeights * n)()
+    for lw in LW:
+        lw.agg_w = lw.self_sum = lw.self_wmax = lw.self_wmin = PTR
+    W = _lib.EdgeWeights(deg_w=PTR if gcn else None, loop_w=PTR if gcn else None, layers=LW)
+    W._keep = LW
+    return W
+
+
+def describe_w(desc, post, wts, rows=70):
+    buf = ctypes.create_string_buffer(512)
+    _lib.check(_lib.load().xpg_forward_describe_w(ctypes.byref(desc), post,
+                                                  ctypes.byref(wts) if wts is not None else None, rows,
+                                                  buf, len(buf)))
+    return buf.value.decode()
+
+
+def workspace_w(desc, post, wts, rows=70):
+    n = ctypes.c_size_t(0)
+    _lib.check(_lib.load().xpg_forward_workspace_w(ctypes.byref(desc), post,
+                                                   ctypes.byref(wts) if wts is not None else None, rows,
+                                                   ctypes.byref(n)))
+    return n.value
+
+
+def _refused(desc, wts, match, post=None):
+    with pytest.raises(RuntimeError, match=match):
+        describe_w(desc, post, wts)
+    with pytest.raises(RuntimeError, match=match):
+        workspace_w(desc, post, wts)
+    y = ctypes.c_void_p(0)
+    rc = _lib.load().xpg_masked_forward_w(ctypes.byref(desc), post, ctypes.byref(wts), y, 70, y, y, 0, y)
+    assert rc == 1  # XPG_EINVAL, before any launch (no workspace, no device pointer read)
+
+
+SUM, MAX = ("sum", "root"), ("max", "root")
+
+
+def test_null_weights_are_the_post_entry_points():
+    for layers, kw in (([(SAGE, 128), (SAGE, 128)], dict(n_nodes=10000, n_tgt=10000)),
+                       ([(SAGE, 128), (SAGE, 128)], {}), ([(GCN, 32), (GCN, 32)], dict(n_nodes=40, n_tgt=8))):
+        desc = make_plan(layers, **kw)
+        assert describe_w(desc, None, None) == describe(desc)
+        n0 = ctypes.c_size_t(0)
+        _lib.check(_lib.load().xpg_forward_workspace(ctypes.byref(desc), 70, ctypes.byref(n0)))
+        assert workspace_w(desc, None, None) == n0.value > 0
+
+
+def test_weighted_plans_take_the_multi_kernel_path():
+    small = dict(n_nodes=40, n_tgt=8)
+    for layers, kw in (([(GCN, 32), (GCN, 32)], small), ([(SUM, 32), (SUM, 32)], small),
+                       ([(SAGE, 128), (SAGE, 128)], dict(n_nodes=10000, n_tgt=10000))):
+        desc = make_plan(layers, **kw)
+        assert describe(desc) != "unfused"  # unweighted: rows / wide
+        assert describe_w(desc, None, _weights(2)) == "unfused weights=k_degree_w+k_agg_w"
+    desc = make_plan_raw([(MAX, 32), (MAX, 32)], raw=True, **small)
+    assert describe_w(desc, None, _weights(2, gcn=False)) == "unfused weights=k_degree_w+k_agg_w"
+    # post tokens follow
+    desc = make_plan([(GCN, 32), (GCN, 32)], **small)
+    desc.layers[1].act = 0
+    P = (_lib.PostDesc * 2)()
+    P[1].norm, P[1].eps, P[1].act, P[1].residual = 1, 1e-5, 1, 1
+    assert describe_w(desc, P, _weights(2)) == "unfused weights=k_degree_w+k_agg_w post2=k_post<layer,1>"
+
+
+def test_weighted_workspace_adds_the_weighted_degrees_of_gcn_plans_only():
+    rows, n0 = 70, 300
+    for layers, gcn in (([(GCN, 32), (GCN, 32)], True), ([(SUM, 32), (SUM, 32)], False)):
+        desc = make_plan(layers)
+        P = (_lib.PostDesc * 2)()  # no post-op; the multi-kernel layout of the same plan
+        base = workspace_w(desc, P, None, rows)
+        extra = (4 * rows * n0 + 255) // 256 * 256 if gcn else 0
+        assert workspace_w(desc, None, _weights(2, gcn), rows) == base + extra
+
+
+def test_host_checks():
+    small = dict(n_nodes=40, n_tgt=8)
+    W = _weights(2)
+    d = make_plan([(GCN, 32), (GCN, 32)], **small)
+    d.edge_masks = 1
+    _refused(d, W, "edge_masks")
+    d = make_plan([(GCN, 32), (GCN, 32)], **small)
+    d.edge_dot = 1
+    _refused(d, W, "edge_dot")
+    d = make_plan([(GCN, 32), (GCN, 32)], **small)
+    d.n_rel = 2
+    _refused(d, W, "n_rel")
+    d = make_plan([(GCN, 32), (GCN, 32)], **small)
+    d.layers[1].tgt_type = PTR
+    _refused(d, W, "tgt_type")
+    for kind in ("att", "att2", "rel"):
+        d = make_plan([((kind,), 32), ((kind,), 32)], **small)
+        _refused(d, W, "ATT / ATT2 / REL")
+    d = make_plan([(GCN, 32), (GCN, 32)], **small)
+    for field in ("agg_w", "self_sum", "self_wmax", "self_wmin"):
+        W2 = _weights(2)
+        setattr(W2.layers[1], field, None)
+        _refused(d, W2, "layer record misses")
+    _refused(d, _weights(2, gcn=False), "deg_w and loop_w")
+    W3 = _weights(2)
+    W3.layers = None
+    _refused(d, W3, "layer records")
+    # without a GCN term deg_w / loop_w are not needed
+    assert "weights=" in describe_w(make_plan([(SUM, 32), (SUM, 32)], **small), None, _weights(2, gcn=False))
+
+
+@pytest.mark.parametrize("path", ["rows", "fused", "wide"])
+def test_forced_paths_are_refused_under_strict(path, monkeypatch):
+    d = make_plan([(GCN, 32), (GCN, 32)], n_nodes=40, n_tgt=8)
+    monkeypatch.setenv("XPG_FORWARD", path)
+    assert "weights=k_degree_w+k_agg_w" in describe_w(d, None, _weights(2))  # not strict: falls back
+    monkeypatch.setenv("XPG_FORWARD_STRICT", "1")
+    with pytest.raises(RuntimeError, match="forced XPG_FORWARD path"):
+        describe_w(d, None, _weights(2))
+    monkeypatch.setenv("XPG_FORWARD", "unfused")
+    assert describe_w(d, None, _weights(2)) == "unfused weights=k_degree_w+k_agg_w"
+
+
+# ------------------------------------------------------------------ Explainer refusals
+def _explainer(arch=None, w="ok", **kw):
+    from bikg_graph_explainability_public_amd.explainer import Explainer
+    ei, wv, x = _graph()
+    feat, eit = torch.as_tensor(x, dtype=torch.float32), torch.as_tensor(ei)
+    wt = torch.as_tensor(wv, dtype=torch.float32) if isinstance(w, str) else w
+    params = dict({"seed": 1, "interpret_samples": 10, "epochs": 8, "optimizer": "adam", "lr": 0.01,
+                   "lr_patience": 10, "l1_lambda": 1e-4}, **kw.pop("params", {}))
+    arch = ConvStack("gcn", [6, 8, 8], [8, 1]).eval() if arch is None else arch
+    args = dict(problem="node_prediction", edge_weight=wt)
+    args.update(kw)
+    return Explainer(args.pop("feat", feat), args.pop("edge_index", eit), arch, params,
+                     args.pop("names", [str(i) for i in range(12)]), None, None, None, **args)
+
+
+def test_explainer_refusals():
+    assert _explainer().edge_weight is not None
+    with pytest.raises(ValueError, match="one weight per edge"):
+        _explainer(w=torch.ones(5))
+    bad = torch.ones(18)
+    bad[3] = float("nan")
+    with pytest.raises(ValueError, match="finite"):
+        _explainer(w=bad)
+    neg = torch.ones(18)
+    neg[3] = -0.5
+    with pytest.raises(ValueError, match=">= 0"):
+        _explainer(w=neg)
+    assert _explainer(ConvStack("graphconv", [6, 8, 8], [8, 1]).eval(), w=neg).edge_weight is neg
+    with pytest.raises(NotImplementedError, match="hetero"):
+        ei, _, x = _graph()
+        _explainer(feat={"n": torch.as_tensor(x, dtype=torch.float32)},
+                   edge_index={("n", "a", "n"): torch.as_tensor(ei)}, names={"n": [str(i) for i in range(12)]})
+    with pytest.raises(NotImplementedError, match="node_types / edge_types"):
+        _explainer(edge_types=torch.zeros(18))
+    with pytest.raises(NotImplementedError, match="edge masks"):
+        _explainer(params={"edge_masks": True}, problem="edge_prediction")
+    with pytest.raises(NotImplementedError, match="link_prediction"):
+        _explainer(problem="link_prediction")
+
+    class NoKeyword(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.inner = ConvStack("gcn", [6, 8, 8], [8, 1])
+
+        def forward(self, x, edge_index):
+            return self.inner(x, edge_index)
+    with pytest.raises(TypeError, match="no edge_weight parameter"):
+        _explainer(NoKeyword().eval())
+    with pytest.raises(TypeError, match="no edge_weight parameter"):
+        pipeline.generic_outputs(NoKeyword().eval(), None, None, None, 0, "node_prediction",
+                                 edge_weight=torch.ones(18))
