@@ -80,6 +80,16 @@ class EdgeWeights(ctypes.Structure):
     _fields_ = [("deg_w", c_vp), ("loop_w", c_vp), ("layers", ctypes.POINTER(LayerWeights))]
 
 
+class LayerEfeat(ctypes.Structure):
+    """xpg_layer_efeat (v27 addendum): one conv layer's edge rows in the layer's CSR orders."""
+    _fields_ = [("agg_e", c_vp), ("self_e", c_vp), ("msg_rows", c_vp)]
+
+
+class EdgeFeats(ctypes.Structure):
+    """xpg_edge_feats (v27 addendum): a plan's edge features; `layers` is a host array."""
+    _fields_ = [("layers", ctypes.POINTER(LayerEfeat))]
+
+
 class WlmParams(ctypes.Structure):
     _fields_ = [("lr", c_f32), ("l1_lambda", c_f32), ("beta1", c_f32), ("beta2", c_f32),
                 ("eps", c_f32), ("weight_decay", c_f32)]
@@ -135,6 +145,15 @@ _SIGS = {
                               ctypes.POINTER(EdgeWeights), c_vp, c_i64, c_vp, c_vp, ctypes.c_size_t, c_vp], c_i32),
     "xpg_forward_describe_w": ([ctypes.POINTER(ForwardPlanDesc), ctypes.POINTER(PostDesc),
                                 ctypes.POINTER(EdgeWeights), c_i64, ctypes.c_char_p, ctypes.c_size_t], c_i32),
+    "xpg_forward_workspace_e": ([ctypes.POINTER(ForwardPlanDesc), ctypes.POINTER(PostDesc),
+                                 ctypes.POINTER(EdgeWeights), ctypes.POINTER(EdgeFeats), c_i64,
+                                 ctypes.POINTER(ctypes.c_size_t)], c_i32),
+    "xpg_masked_forward_e": ([ctypes.POINTER(ForwardPlanDesc), ctypes.POINTER(PostDesc),
+                              ctypes.POINTER(EdgeWeights), ctypes.POINTER(EdgeFeats), c_vp, c_i64, c_vp, c_vp,
+                              ctypes.c_size_t, c_vp], c_i32),
+    "xpg_forward_describe_e": ([ctypes.POINTER(ForwardPlanDesc), ctypes.POINTER(PostDesc),
+                                ctypes.POINTER(EdgeWeights), ctypes.POINTER(EdgeFeats), c_i64, ctypes.c_char_p,
+                                ctypes.c_size_t], c_i32),
     "xpg_post_rows": ([c_vp, c_i64, c_i64, c_i64, ctypes.POINTER(PostDesc), c_vp, c_i64, c_i64, c_i64,
                        c_vp, c_vp], c_i32),
     "xpg_post_describe": ([c_i64, c_i64, c_i64, ctypes.POINTER(PostDesc), ctypes.c_char_p,

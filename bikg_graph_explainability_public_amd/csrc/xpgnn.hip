@@ -1308,6 +1308,126 @@ __global__ __launch_bounds__(256) void k_agg_w(AggWArgs w) {
   }
 }
 
+// ------------------------------------------------------------------------------------ edge features
+// Graphs with edge features (xpg_edge_feats, GINEConv; the rules are in xpgnn.h).  A kernel of its
+// own, so that k_agg / k_agg_w keep their code and registers.
+struct AggEArgs {
+  AggArgs a;              // as k_agg's raw / deeper-layer form; self_ptr set, bits / agg_eid / tgt_type unset
+  const float* agg_e;     // [n_edges][width] edge row of each in-edge (the index of agg_f0)
+  const float* self_e;    // [n_self][width] edge row of each self-loop (the index of self_eid)
+  const float* msg_agg;   // MSG: [n_edges][width] relu(x_j + agg_e[e]), the whole message
+  const float* msg_self;  // MSG: [n_self][width] relu(x_t + self_e[k])
+};
+
+__device__ __forceinline__ float4 relu_add4(const float4 x, const float4 e) {
+  const float a = x.x + e.x, b = x.y + e.y, c = x.z + e.z, d = x.w + e.w;
+  return make_float4(a > 0.f ? a : 0.f, b > 0.f ? b : 0.f, c > 0.f ? c : 0.f, d > 0.f ? d : 0.f);
+}
+
+// Masked aggregation with edge features for one conv layer, in the aggregate-then-transform form:
+// k_agg_w's item and lane mapping and k_agg's keep tests (node masks only); SUM and ROOT terms.  A
+// SUM term of a kept target adds relu(x_t + self_e[k]) over its self-loops, then relu(x_j + agg_e[e])
+// over its kept in-edges in CSR order: EB edges' F_0 positions, keep tests and then both rows (the
+// source's and the edge's) are issued before the first add.  MSG (layer 1: the sources are the raw
+// feature rows shared by every mask row): the plan holds each edge's whole message, one row to
+// load and the same fp32 values to add.
+template <bool MSG, int LPS, int NV>
+__global__ __launch_bounds__(256) void k_agg_e(AggEArgs w) {
+  const AggArgs& a = w.a;
+  const int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t item = gid / LPS;
+  const int sub = static_cast<int>(gid - item * LPS);
+  if (item >= a.rows * a.n_tgt) return;
+  const int64_t b = item / a.n_tgt;
+  const int t = static_cast<int>(item - b * a.n_tgt);
+  const float* kb = a.kin + b * (int64_t)a.n_rel * a.kpitch;
+  const uint32_t* mrow = a.mbits ? a.mbits + b * a.words : nullptr;
+  const int t0 = a.tgt_f0[t];
+  const int tp = a.tgt_prev[t];
+  const float* base = a.hprev + b * a.hstride;
+  const float4* selfrow = reinterpret_cast<const float4*>(base + (int64_t)tp * a.width);
+  const float* etab = MSG ? w.msg_agg : w.agg_e;
+  const float* stab = MSG ? w.msg_self : w.self_e;
+
+  for (int k = 0; k < a.n_terms; ++k) {
+    float4 s[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) s[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (a.kind[k] == XPG_TERM_ROOT) {
+#pragma unroll
+      for (int j = 0; j < NV; ++j) s[j] = selfrow[sub + j * LPS];
+    } else if (kb[(int64_t)a.rel[k] * a.kpitch + t0] >= 0.f) {  // SUM; a masked-out target keeps no edge
+      const int r = a.rel[k];
+      const int* pp = a.agg_ptr + (int64_t)r * (a.n_tgt + 1);
+      const int* sp = a.self_ptr + (int64_t)r * (a.n_tgt + 1);
+      {
+        float4 x[NV];
+        if (!MSG) {
+#pragma unroll
+          for (int j = 0; j < NV; ++j) x[j] = selfrow[sub + j * LPS];
+        }
+        for (int e = sp[t]; e < sp[t + 1]; ++e) {
+          const float4* er = reinterpret_cast<const float4*>(stab + (int64_t)e * a.width);
+#pragma unroll
+          for (int j = 0; j < NV; ++j) {
+            float4 v = er[sub + j * LPS];
+            if (!MSG) v = relu_add4(x[j], v);
+            s[j].x += v.x; s[j].y += v.y; s[j].z += v.z; s[j].w += v.w;
+          }
+        }
+      }
+      // two rows per edge in flight without MSG: half of k_agg's EB there
+      constexpr int EB = (NV >= 4 ? 2 : NV == 2 ? 4 : 8) / (MSG ? 1 : 2);
+      const int e_end = pp[t + 1];
+      for (int eb = pp[t]; eb < e_end; eb += EB) {
+        bool kp[EB];
+        int up[EB], kx[EB];
+#pragma unroll
+        for (int q = 0; q < EB; ++q) up[q] = a.agg_f0[eb + q < e_end ? eb + q : eb];
+        if (mrow) {
+#pragma unroll
+          for (int q = 0; q < EB; ++q) kx[q] = a.f0_node[up[q]];
+#pragma unroll
+          for (int q = 0; q < EB; ++q) kp[q] = bit_of(mrow, kx[q]);
+        } else {
+#pragma unroll
+          for (int q = 0; q < EB; ++q) kp[q] = kb[(int64_t)r * a.kpitch + up[q]] >= 0.f;
+        }
+#pragma unroll
+        for (int q = 0; q < EB; ++q) {
+          kp[q] = kp[q] && eb + q < e_end;
+          if (!MSG) up[q] = a.agg_src[eb + q < e_end ? eb + q : eb];
+        }
+        float4 v[EB][NV], ev[EB][NV];
+#pragma unroll
+        for (int q = 0; q < EB; ++q) {
+          const int e = eb + q < e_end ? eb + q : eb;
+          const float4* er = reinterpret_cast<const float4*>(etab + (int64_t)e * a.width);
+          const float4* src = reinterpret_cast<const float4*>(base + (int64_t)up[q] * a.width);
+#pragma unroll
+          for (int j = 0; j < NV; ++j) {
+            ev[q][j] = kp[q] ? er[sub + j * LPS] : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (!MSG) v[q][j] = kp[q] ? src[sub + j * LPS] : make_float4(0.f, 0.f, 0.f, 0.f);
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < EB; ++q) {
+          if (kp[q]) {
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+              const float4 m = MSG ? ev[q][j] : relu_add4(v[q][j], ev[q][j]);
+              s[j].x += m.x; s[j].y += m.y; s[j].z += m.z; s[j].w += m.w;
+            }
+          }
+        }
+      }
+    }
+    float4* o = reinterpret_cast<float4*>(a.out + item * a.out_ld + (int64_t)k * a.width);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) o[sub + j * LPS] = s[j];
+  }
+}
+
 // ------------------------------------------------------------------------------------ attention
 // Graph attention (XPG_TERM_ATT, GATConv; the rules are in xpgnn.h).  Layers of ATT terms run on
 // kernels of their own: the per-edge weight depends on the mask row through a softmax over the
@@ -6845,6 +6965,39 @@ int weights_plan_check(const xpg_forward_plan* p, const xpg_edge_weights* wts) {
   return XPG_OK;
 }
 
+// the host checks of an edge-featured plan (xpgnn.h, xpg_edge_feats): before any launch, and
+// without reading through a device pointer
+int feats_plan_check(const xpg_forward_plan* p, const xpg_edge_weights* wts, const xpg_edge_feats* fe) {
+  if (!fe) return XPG_OK;
+  XPG_REQ(p && p->layers && p->n_layers >= 1 && p->n_layers <= 64, "plan: 1..64 conv layers required");
+  XPG_REQ(!wts, "masked_forward: edge features and edge weights together are not supported");
+  XPG_REQ(!p->edge_masks, "masked_forward: edge features do not take edge-mask plans (edge_masks)");
+  XPG_REQ(!p->edge_dot, "masked_forward: edge features do not take a link decoder (edge_dot)");
+  XPG_REQ(p->n_rel == 1, "masked_forward: edge features take one relation (n_rel > 1)");
+  XPG_REQ(fe->layers != nullptr, "masked_forward: edge features without their layer records");
+  for (int l = 0; l < p->n_layers; ++l) {
+    const xpg_layer_desc& ly = p->layers[l];
+    XPG_REQ(ly.tgt_type == nullptr && ly.n_types <= 1,
+            "masked_forward: edge features do not take multi-node-type plans (tgt_type)");
+    XPG_REQ(ly.n_terms >= 1 && ly.n_terms <= XPG_MAX_TERMS, "layer: 1..8 terms");
+    bool sum = false;
+    for (int k = 0; k < ly.n_terms; ++k) {
+      const int kind = ly.terms[k].kind;
+      XPG_REQ(kind == XPG_TERM_SUM || kind == XPG_TERM_ROOT,
+              "masked_forward: edge features take SUM / ROOT terms only (no ATT / ATT2 / REL / GCN / MEAN / MAX)");
+      sum = sum || kind == XPG_TERM_SUM;
+    }
+    XPG_REQ(ly.weight && ly.f_in_pad > 0,
+            "masked_forward: edge features: every layer takes the aggregate-then-transform form (weight, f_in_pad)");
+    if (!sum) continue;  // a ROOT-only layer (the second Linear of the MLP) reads no table
+    const xpg_layer_efeat& le = fe->layers[l];
+    XPG_REQ(ly.self_ptr != nullptr, "masked_forward: edge features: a SUM layer needs self_ptr");
+    XPG_REQ(le.agg_e && le.self_e, "masked_forward: edge features: a layer record misses agg_e / self_e");
+    XPG_REQ(l == 0 || !le.msg_rows, "masked_forward: edge features: msg_rows belongs to layer 1 only");
+  }
+  return XPG_OK;
+}
+
 // node-type-gated terms (multi-node-type HeteroConv) run on the multi-kernel path only
 bool plan_multi_type(const xpg_forward_plan* p) {
   for (int l = 0; l < p->n_layers; ++l)
@@ -7131,6 +7284,26 @@ int launch_agg_w(const AggWArgs& w, hipStream_t st) {
   XPG_AGG_W(8, 1) XPG_AGG_W(16, 1) XPG_AGG_W(32, 1) XPG_AGG_W(64, 1) XPG_AGG_W(64, 2) XPG_AGG_W(64, 4)
   XPG_AGG_W(24, 1) XPG_AGG_W(40, 1) XPG_AGG_W(48, 1) XPG_AGG_W(56, 1)
 #undef XPG_AGG_W
+  return fail(XPG_EINVAL, "agg: unsupported row width " + std::to_string(a.width));
+}
+
+// k_agg_e for one layer of an edge-featured plan: launch_agg_w's lane mapping
+template <bool MSG>
+int launch_agg_e(const AggEArgs& w, hipStream_t st) {
+  const AggArgs& a = w.a;
+  XPG_REQ(a.width % 32 == 0 && a.width > 0, "agg: row width must be a positive multiple of 32");
+  const int f4 = a.width / 4;
+  const int lps = f4 >= 64 ? 64 : f4;
+  const int nv = f4 / lps;
+  XPG_REQ(f4 % lps == 0 && (nv == 1 || nv == 2 || nv == 4), "agg: unsupported row width");
+  const int64_t threads = a.rows * a.n_tgt * lps;
+  if (threads == 0) return XPG_OK;
+  dim3 grid(static_cast<unsigned>(cdiv(threads, 256))), block(256);
+#define XPG_AGG_E(LPS, NV) \
+  if (lps == LPS && nv == NV) { hipLaunchKernelGGL((k_agg_e<MSG, LPS, NV>), grid, block, 0, st, w); XPG_LAUNCHED(); return XPG_OK; }
+  XPG_AGG_E(8, 1) XPG_AGG_E(16, 1) XPG_AGG_E(32, 1) XPG_AGG_E(64, 1) XPG_AGG_E(64, 2) XPG_AGG_E(64, 4)
+  XPG_AGG_E(24, 1) XPG_AGG_E(40, 1) XPG_AGG_E(48, 1) XPG_AGG_E(56, 1)
+#undef XPG_AGG_E
   return fail(XPG_EINVAL, "agg: unsupported row width " + std::to_string(a.width));
 }
 
@@ -8601,7 +8774,15 @@ int xpg_forward_workspace_post(const xpg_forward_plan* plan, const xpg_post_desc
 // Edge weights add the weighted degrees of a GCN plan at the end of that layout.
 int xpg_forward_workspace_w(const xpg_forward_plan* plan, const xpg_post_desc* post, const xpg_edge_weights* wts,
                             int64_t rows, size_t* bytes) {
+  return xpg_forward_workspace_e(plan, post, wts, nullptr, rows, bytes);
+}
+
+// Edge features add nothing to that layout (the multi-kernel path's).
+int xpg_forward_workspace_e(const xpg_forward_plan* plan, const xpg_post_desc* post, const xpg_edge_weights* wts,
+                            const xpg_edge_feats* feats, int64_t rows, size_t* bytes) {
   int rc = weights_plan_check(plan, wts);
+  if (rc) return rc;
+  rc = feats_plan_check(plan, wts, feats);
   if (rc) return rc;
   WsLayout L;
   rc = layout_ws(plan, rows, &L, wts);
@@ -8609,7 +8790,7 @@ int xpg_forward_workspace_w(const xpg_forward_plan* plan, const xpg_post_desc* p
   rc = post_plan_check(plan, post);
   if (rc) return rc;
   WideWs W;
-  if (!plan_has_post(plan, post) && !wts && wide_wanted(plan) && wide_layout(plan, rows, &W) == 0) {
+  if (!plan_has_post(plan, post) && !wts && !feats && wide_wanted(plan) && wide_layout(plan, rows, &W) == 0) {
     *bytes = W.total;  // 32-row passes: one buffer set, or two when rows > 32
     return XPG_OK;
   }
@@ -8628,9 +8809,16 @@ int xpg_forward_describe_post(const xpg_forward_plan* p, const xpg_post_desc* po
 
 int xpg_forward_describe_w(const xpg_forward_plan* p, const xpg_post_desc* post, const xpg_edge_weights* wts,
                            int64_t rows, char* buf, size_t n) {
+  return xpg_forward_describe_e(p, post, wts, nullptr, rows, buf, n);
+}
+
+int xpg_forward_describe_e(const xpg_forward_plan* p, const xpg_post_desc* post, const xpg_edge_weights* wts,
+                           const xpg_edge_feats* feats, int64_t rows, char* buf, size_t n) {
   XPG_REQ(buf != nullptr && n > 0, "forward_describe: no buffer");
   buf[0] = 0;
   int rc = weights_plan_check(p, wts);
+  if (rc) return rc;
+  rc = feats_plan_check(p, wts, feats);
   if (rc) return rc;
   WsLayout L;
   rc = layout_ws(p, rows, &L, wts);
@@ -8641,11 +8829,12 @@ int xpg_forward_describe_w(const xpg_forward_plan* p, const xpg_post_desc* post,
   const bool has_post = plan_has_post(p, post);
   WideWs W;
   FwdPath path;
-  rc = forward_route(p, rows, &W, &path, nullptr, has_post || wts != nullptr);
+  rc = forward_route(p, rows, &W, &path, nullptr, has_post || wts != nullptr || feats != nullptr);
   if (rc) return rc;
   if (path == kPathNone) return fail(XPG_EINVAL, kStrictMsg);
   std::string s = kPathName[path];
   if (wts) s += " weights=k_degree_w+k_agg_w";  // a weighted plan's degree and aggregation kernels
+  if (feats) s += " efeat=k_agg_e";              // an edge-featured plan's aggregation kernel
   if (path == kPathWide) {
     WidePick pick;
     rc = wide_select(p, W, &pick);
@@ -8729,7 +8918,15 @@ int xpg_masked_forward_post(const xpg_forward_plan* p, const xpg_post_desc* post
 int xpg_masked_forward_w(const xpg_forward_plan* p, const xpg_post_desc* post, const xpg_edge_weights* wts,
                          const uint32_t* bits, int64_t rows, float* y, void* workspace, size_t workspace_bytes,
                          xpg_stream_t stream) {
+  return xpg_masked_forward_e(p, post, wts, nullptr, bits, rows, y, workspace, workspace_bytes, stream);
+}
+
+int xpg_masked_forward_e(const xpg_forward_plan* p, const xpg_post_desc* post, const xpg_edge_weights* wts,
+                         const xpg_edge_feats* feats, const uint32_t* bits, int64_t rows, float* y, void* workspace,
+                         size_t workspace_bytes, xpg_stream_t stream) {
   int rc = weights_plan_check(p, wts);
+  if (rc) return rc;
+  rc = feats_plan_check(p, wts, feats);
   if (rc) return rc;
   WsLayout L;
   rc = layout_ws(p, rows, &L, wts);
@@ -8749,7 +8946,7 @@ int xpg_masked_forward_w(const xpg_forward_plan* p, const xpg_post_desc* post, c
   // hold (a wide plan returns before `go` is read; its workspace is checked below)
   const bool ready = workspace_bytes >= L.total && rows != 0;
   const FwdLaunch go{bits, y, st, workspace ? reinterpret_cast<int*>(static_cast<char*>(workspace) + L.ctl) : nullptr};
-  rc = forward_route(p, rows, &W, &path, ready ? &go : nullptr, has_post || wts != nullptr);
+  rc = forward_route(p, rows, &W, &path, ready ? &go : nullptr, has_post || wts != nullptr || feats != nullptr);
   if (rc) return rc;
   if (path == kPathWide) {
     XPG_REQ(workspace_bytes >= W.total, "masked_forward: workspace too small");
@@ -8808,6 +9005,23 @@ int xpg_masked_forward_w(const xpg_forward_plan* p, const xpg_post_desc* post, c
   }
   // a layer's aggregation: k_agg / k_agg_l1_rows, or k_agg_w with the layer's weights
   auto agg_launch = [&](const AggArgs& a, bool l1, int l) -> int {
+    if (feats) {  // feats_plan_check: never the table form; a ROOT-only layer reads no edge table
+      AggEArgs w;
+      w.a = a;
+      w.a.self_ptr = p->layers[l].self_ptr;
+      const xpg_layer_efeat& le = feats->layers[l];
+      w.agg_e = le.agg_e;
+      w.self_e = le.self_e;
+      w.msg_agg = w.msg_self = nullptr;
+      // layer 1's stored messages (XPG_EFEAT_MSG=0, diagnostics: the two-row form there too)
+      const char* msg_env = getenv("XPG_EFEAT_MSG");
+      if (l == 0 && le.msg_rows && !(msg_env && std::strcmp(msg_env, "0") == 0)) {
+        w.msg_agg = le.msg_rows;
+        w.msg_self = le.msg_rows + (int64_t)p->layers[l].n_edges * a.width;
+        return launch_agg_e<true>(w, st);
+      }
+      return launch_agg_e<false>(w, st);
+    }
     if (!wts) return l1 ? launch_agg<true>(a, st) : launch_agg<false>(a, st);
     AggWArgs w;
     w.a = a;

@@ -145,11 +145,13 @@ class Data:
 
     # -------------------------------------------------------------- computational graph
     def comp_graph(self, ind, n_hops, problem, names, node_types=None, edge_types=None,
-                   return_pos=False, edge_weight=None):
+                   return_pos=False, edge_weight=None, edge_attr=None):
         """data.py:281-361 — k-hop computational subgraph with one hop more than the model.
         `return_pos` appends the positions of `sub_names` in `names` (int64 numpy array);
         `edge_weight` ([E]) appends, last, the kept edges' weights (the edge mask that slices
-        `edge_types`; weight 1 for the self-loop a subgraph without edges is given)."""
+        `edge_types`; weight 1 for the self-loop a subgraph without edges is given);
+        `edge_attr` ([E, D]) appends, last, the kept edges' attribute rows (a zero row for that
+        self-loop)."""
         hops = n_hops + 1
         n = self.feat.shape[0]
         subset, sub_ei, sub_ind, emask = k_hop_subgraph(ind, hops, self.edge_index, n)
@@ -161,6 +163,12 @@ class Data:
                                   device=self.edge_index.device)
             if sub_w is not None:
                 sub_w = torch.ones(1, dtype=sub_w.dtype, device=sub_w.device)
+        sub_a = None
+        if edge_attr is not None:
+            ea = edge_attr.reshape(-1, 1) if edge_attr.dim() == 1 else edge_attr
+            sub_a = ea[torch.where(emask)[0]]
+            if sub_a.shape[0] == 0:  # the fabricated self-loop carries a zero row
+                sub_a = torch.zeros((1, ea.shape[1]), dtype=ea.dtype, device=ea.device)
         sub_feat = self.feat[subset]
         sub_nt = node_types[subset] if node_types is not None else None
         sub_et = edge_types[torch.where(emask)[0]] if edge_types is not None else None
@@ -170,7 +178,8 @@ class Data:
         pos = pos.cpu().numpy()
         sub_names = take_names(names, pos)
         out = (sub_feat, sub_ei, sub_names, sub_ind, sub_nt, sub_et) + ((pos,) if return_pos else ())
-        return out + (sub_w,) if edge_weight is not None else out
+        out = out + (sub_w,) if edge_weight is not None else out
+        return out + (sub_a,) if edge_attr is not None else out
 
     def edge_comp_graph(self, ind, n_hops, names, return_pos=False):
         """Computational graph of an edge problem (edge masks mode; the reference's data.py:281-361
@@ -216,15 +225,19 @@ class Data:
         tiled = ei.int().repeat(1, B) + off
         return keep, tiled
 
-    def perturb_node(self, mask, edge_type=None, edge_weight=None):
+    def perturb_node(self, mask, edge_type=None, edge_weight=None, edge_attr=None):
         """data.py:453-498.  With `edge_weight` ([E], one per edge) a third value is returned:
-        the kept edges' weights, in the kept edges' order."""
+        the kept edges' weights, in the kept edges' order; with `edge_attr` ([E, D]) instead, the
+        kept edges' attribute rows."""
         keep, tiled = self.build_edge_mask(mask)
         et = None
         if edge_type is not None:
             et = edge_type.int().repeat(mask.shape[0])[keep]
         if edge_weight is not None:
             return tiled[:, keep], et, edge_weight.reshape(-1).to(mask.device).repeat(mask.shape[0])[keep]
+        if edge_attr is not None:
+            ea = edge_attr.reshape(-1, 1) if edge_attr.dim() == 1 else edge_attr
+            return tiled[:, keep], et, ea.to(mask.device).repeat(mask.shape[0], 1)[keep]
         return tiled[:, keep], et
 
     def perturb_edge(self, mask, edge_type=None):
@@ -243,10 +256,19 @@ class Data:
         """data.py:556-589."""
         return self.feat.repeat(n, 1), (node_type.repeat(n) if node_type is not None else None)
 
-    def perturbator(self, mask, problem, node_type=None, edge_type=None, edge_weight=None):
+    def perturbator(self, mask, problem, node_type=None, edge_type=None, edge_weight=None,
+                    edge_attr=None):
         """data.py:591-648 — B-fold union graph of the masked copies (generic black-box path).
-        With `edge_weight` (node masks only) the kept edges' weights are returned as a fifth value."""
+        With `edge_weight` (node masks only) the kept edges' weights are returned as a fifth value;
+        with `edge_attr` (node masks only) the kept edges' attribute rows are."""
         feat, nt = self.concat_features(mask.shape[0], node_type)
+        if edge_attr is not None:
+            if edge_weight is not None:
+                raise ValueError("edge_attr and edge_weight together are not supported")
+            if "edge" in problem:
+                raise NotImplementedError("edge_attr under edge masks is not supported")
+            ei, et, pea = self.perturb_node(mask, edge_type, edge_attr=edge_attr)
+            return feat.float(), nt, ei, et, pea
         if edge_weight is not None:
             if "edge" in problem:
                 raise NotImplementedError("edge_weight under edge masks is not supported")

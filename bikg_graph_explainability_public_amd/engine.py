@@ -785,6 +785,77 @@ def weight_arrays(arr, src, dst, w):
     return out
 
 
+_EDGE_TABLE_MAX_BYTES = 1 << 30  # the edge tables of an edge-featured plan (a resource guard)
+
+
+def check_edge_attr(edge_attr, n_edges):
+    """float32 numpy [n_edges, D] copy of `edge_attr`: one finite float row per edge (a 1-D tensor
+    of length n_edges is D = 1); ValueError otherwise."""
+    a = np.asarray(torch.as_tensor(edge_attr).detach().cpu().numpy())
+    if a.ndim == 1:
+        a = a.reshape(-1, 1)
+    if a.ndim != 2 or a.shape[0] != int(n_edges) or a.shape[1] < 1:
+        raise ValueError(f"edge_attr must give one row per edge ({int(n_edges)}), got shape "
+                         f"{tuple(a.shape)}")
+    if not np.issubdtype(a.dtype, np.floating):
+        raise ValueError("edge_attr must be a floating-point tensor")
+    if not np.isfinite(a).all():
+        raise ValueError("edge_attr must be finite (NaN or inf found)")
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def edge_feature_arrays(arr, convs, ea, x0):
+    """The edge features of a plan in its CSR orders (xpgnn.h, xpg_edge_feats), on the host.
+    `arr`: plan_arrays(..., rel_eid=[arange(E)]) of a one-relation graph, so that agg_eid / self_eid
+    are edge ids; `convs`: the program's conv layers; ea [E, D] float32 the attribute rows; x0
+    [n0, f_in] float32 the feature rows of the F_0 nodes.  Per conv layer with a "sum" term (None
+    for a ROOT-only layer) {"agg_e" [n_edges, f_in_pad], "self_e" [n_self, f_in_pad]}, float32 with
+    zero padded columns: the rows of E_l = ea edge_lin_w^T + edge_lin_b (fp64, rounded once; ea
+    itself without an edge map) gathered by the CSRs' edge ids.  Layer 1 also holds "msg_rows"
+    [n_edges + n_self, f_in_pad]: relu(x_j + agg_e[e]) per in-edge, then relu(x_t + self_e[k]) per
+    self-loop, in fp32 (the sources of layer 1 are the feature rows, the same for every mask row).
+    ValueError for attribute rows whose width fits neither the edge map nor the layer input."""
+    ea = np.asarray(ea, dtype=np.float32)
+    out = []
+    for li, (conv, lay) in enumerate(zip(convs, arr["layers"])):
+        sums = [t for t in conv.terms if t.kind == "sum"]
+        if not sums:
+            out.append(None)
+            continue
+        term = sums[0]
+        if term.edge_lin_w is not None:
+            w = term.edge_lin_w.detach().cpu().numpy().astype(np.float64)
+            if w.shape[1] != ea.shape[1]:
+                raise ValueError(f"edge_attr of width {ea.shape[1]} on a GINEConv with edge_dim {w.shape[1]}")
+            ee = ea.astype(np.float64) @ w.T
+            if term.edge_lin_b is not None:
+                ee = ee + term.edge_lin_b.detach().cpu().numpy().astype(np.float64)
+            ee = ee.astype(np.float32)
+        else:
+            if ea.shape[1] != conv.f_in:
+                raise ValueError(f"edge_attr of width {ea.shape[1]} on a GINEConv(edge_dim=None) whose "
+                                 f"input has width {conv.f_in}")
+            ee = ea
+        pad = _rup(conv.f_in, 32)
+        agg_eid = np.asarray(lay["agg_eid"], dtype=np.int64)
+        self_eid = np.asarray(lay["self_eid"], dtype=np.int64)
+        agg_e = np.zeros((agg_eid.size, pad), dtype=np.float32)
+        agg_e[:, :conv.f_in] = ee[agg_eid]
+        self_e = np.zeros((self_eid.size, pad), dtype=np.float32)
+        self_e[:, :conv.f_in] = ee[self_eid]
+        d = {"agg_e": agg_e, "self_e": self_e}
+        if li == 0:
+            xp = np.zeros((x0.shape[0], pad), dtype=np.float32)
+            xp[:, :conv.f_in] = np.asarray(x0, dtype=np.float32)
+            sptr = np.asarray(lay["self_ptr"], dtype=np.int64)
+            tgt = np.repeat(np.arange(sptr.size - 1), np.diff(sptr))  # F_1 is a prefix of F_0
+            msg = np.concatenate([xp[np.asarray(lay["agg_f0"], dtype=np.int64)] + agg_e,
+                                  xp[tgt] + self_e])
+            d["msg_rows"] = np.maximum(msg, np.float32(0))
+        out.append(d)
+    return out
+
+
 _STAGING = {}  # device index -> [next slot, [(pinned host tensor, event of its last copy)] * _STAGING_SLOTS]
 _STAGING_MAX = 16 << 20  # bytes: larger arrays take the pageable copy
 _STAGING_SLOTS = 4  # a call's uploads take consecutive slots: none waits for the previous copy
@@ -882,7 +953,7 @@ class ForwardPlan:
     """Receptive-field plan of one (subgraph, model program, query set)."""
 
     def __init__(self, program, sub_feat, rel_edges, queries, device=None, node_type=None,
-                 edge_cols=None, link=None, edge_weight=None):
+                 edge_cols=None, link=None, edge_weight=None, edge_attr=None):
         """`node_type` ([S] node type of every subgraph node) is required by multi-node-type
         programs: per layer, every target's type gates the relation terms (xpgnn.h).
 
@@ -903,7 +974,14 @@ class ForwardPlan:
         of GCNConv / GraphConv): the plan carries the weights gathered into its CSR orders
         (weight_arrays; xpgnn.h, xpg_edge_weights) and runs on k_degree_w / k_agg_w.  Node masks,
         one relation, one node type, gcn / mean / sum / max / root terms only; weights >= 0 with a
-        gcn term.  None: the plan is exactly the unweighted one."""
+        gcn term.  None: the plan is exactly the unweighted one.
+
+        `edge_attr` ([E, D] or [E], one finite float row per edge of the one relation; PyG 2.0.4's
+        edge_attr of GINEConv): needed by, and only taken by, a program compiled with
+        edge_attr=True.  The plan carries each layer's mapped edge rows gathered into its CSR
+        orders (edge_feature_arrays; xpgnn.h, xpg_edge_feats) and runs on k_agg_e; every layer takes
+        the aggregate-then-transform form, so the input may be at most 256 columns wide after
+        padding to 32.  Node masks, one relation, one node type; not together with edge_weight."""
         device = torch.device(device) if device is not None else sub_feat.device
         _lib.require_device(torch.empty(0, device=device), "plan device")
         if len(program.convs) == 0:
@@ -958,6 +1036,23 @@ class ForwardPlan:
                 raise ValueError("edge_weight on multi-relation or multi-node-type graphs is not supported")
             w_np = check_edge_weight(edge_weight, rel_np[0].shape[1], "gcn" in kinds)
             # the CSRs carry each entry's edge id, which gathers the weights below
+            rel_eid = [np.arange(rel_np[0].shape[1], dtype=np.int64)]
+        ea_np = None
+        if edge_attr is not None or getattr(program, "edge_featured", False):
+            if edge_attr is not None and edge_weight is not None:
+                raise ValueError("edge_attr and edge_weight together are not supported")
+            if edge_attr is None:
+                raise ValueError("a program compiled for edge features needs the plan's edge_attr")
+            kinds = {t.kind for c in program.convs for t in c.terms}
+            if not getattr(program, "edge_featured", False) or not kinds <= {"sum", "root"}:
+                raise ValueError("edge_attr on a program that was not compiled for edge features "
+                                 "(GINEConv only) is not supported")
+            if self.edge_masks or link is not None:
+                raise ValueError("edge_attr on edge-mask plans is not supported")
+            if self.n_rel != 1 or program.n_types > 1:
+                raise ValueError("edge_attr on multi-relation or multi-node-type graphs is not supported")
+            ea_np = check_edge_attr(edge_attr, rel_np[0].shape[1])
+            # the CSRs carry each entry's edge id, which gathers the edge rows below
             rel_eid = [np.arange(rel_np[0].shape[1], dtype=np.int64)]
         arr = plan_arrays(S, rel_np, queries, L, rel_eid)
         self.arrays = arr
@@ -1045,12 +1140,13 @@ class ForwardPlan:
             ld.n_edges = int(arr["layers"][li]["agg_src"].size)
             # max is not linear: a first conv with a "max" term takes the raw form (aggregate the
             # raw feature rows, then the dense product), like every deeper layer
-            raw = li == 0 and any(t.kind == "max" for t in terms)
+            raw = li == 0 and (any(t.kind == "max" for t in terms) or ea_np is not None)
             if raw:
                 prev_pad = _rup(f_in0, 32)
                 if prev_pad > 256:
                     raise ValueError("a first conv with a max term and an input wider than 256 "
-                                     "is not supported")
+                                     "is not supported" if ea_np is None else
+                                     "edge features with an input wider than 256 are not supported")
             ld.f_in_pad = prev_pad if (li > 0 or raw) else 0
             nz = lambda a: a if a.size else np.zeros(1)
             self._i32(ld, "tgt_prev", np.arange(n_t))  # F_l is a prefix of F_{l-1}
@@ -1068,6 +1164,8 @@ class ForwardPlan:
                 self._i32(ld, "agg_eid", nz(lay["agg_eid"]))
                 self._i32(ld, "self_ptr", lay["self_ptr"])
                 self._i32(ld, "self_eid", nz(lay["self_eid"]))
+            if ea_np is not None:  # k_agg_e walks the self-loops; their rows are in self_eid's order
+                self._i32(ld, "self_ptr", lay["self_ptr"])
             n_types = program.n_types
 
             def make_bias(conv=conv, f_out_pad=f_out_pad):
@@ -1319,6 +1417,35 @@ class ForwardPlan:
                 lw = self._layer_weights[li]
                 lw.agg_w, lw.self_sum, lw.self_wmax, lw.self_wmin = (at(2 + 4 * li + j) for j in range(4))
             self._weights = _lib.EdgeWeights(deg_w=at(0), loop_w=at(1), layers=self._layer_weights)
+        # edge features (xpgnn.h, xpg_edge_feats): every table in one upload
+        self._feats = None
+        self.edge_feature_arrays = None
+        if ea_np is not None:
+            # a resource guard, before anything is built: rows of f_in_pad floats per CSR entry of
+            # every SUM layer (twice for layer 1, which also stores the messages)
+            need = sum(4 * _rup(c.f_in, 32) * (len(lay["agg_eid"]) + len(lay["self_eid"])) * (2 if li == 0 else 1)
+                       for li, (c, lay) in enumerate(zip(program.convs, arr["layers"]))
+                       if any(t.kind == "sum" for t in c.terms))
+            if need > _EDGE_TABLE_MAX_BYTES:
+                raise ValueError(f"edge-feature tables of {need >> 20} MiB exceed "
+                                 f"{_EDGE_TABLE_MAX_BYTES >> 20} MiB")
+            x0 = sub_feat.detach().to(dtype=torch.float32).cpu().numpy()[np.asarray(fr[0], dtype=np.int64)]
+            fa = edge_feature_arrays(arr, program.convs, ea_np, x0)
+            self.edge_feature_arrays = fa
+            names = ("agg_e", "self_e", "msg_rows")
+            parts = [(li, k, lay[k].reshape(-1)) for li, lay in enumerate(fa) if lay is not None
+                     for k in names if k in lay]
+            parts = [(li, k, a if a.size else np.zeros(1, np.float32)) for li, k, a in parts]
+            offs = np.concatenate([[0], np.cumsum([(a.size + 15) // 16 * 16 for _, _, a in parts])]).astype(np.int64)
+            host = np.zeros(int(offs[-1]), dtype=np.float32)
+            for (_, _, a), o in zip(parts, offs):
+                host[o:o + a.size] = a
+            buf = h2d(host, device)
+            self._keep.append(buf)
+            self._layer_efeat = (_lib.LayerEfeat * L)()
+            for (li, k, _), o in zip(parts, offs):
+                setattr(self._layer_efeat[li], k, buf.data_ptr() + 4 * int(o))
+            self._feats = _lib.EdgeFeats(layers=self._layer_efeat)
         self._ws = None
         self._ws_stream = None  # raw handle of the stream that last used self._ws
 
@@ -1361,6 +1488,8 @@ class ForwardPlan:
     def _entry(self, name):
         """The entry point and its leading arguments: `name`(plan, ...), or with post-ops
         `name`_post(plan, post records, ...)."""
+        if self._feats is not None:  # `name`_e(plan, post records or NULL, NULL weights, features, ...)
+            return name + "_e", (ctypes.byref(self.desc), self._post, None, ctypes.byref(self._feats))
         if self._weights is not None:  # `name`_w(plan, post records or NULL, weights, ...)
             return name + "_w", (ctypes.byref(self.desc), self._post, ctypes.byref(self._weights))
         if self._post is None:
@@ -1377,7 +1506,8 @@ class ForwardPlan:
         """The path forward() takes for `rows` mask rows under the current environment: "rows",
         "fused", "unfused", or "wide l1=<kernel> l2=<kernel>" with the kernels' template
         arguments; a plan with post-ops: "unfused post<l>=k_post<NORM,RES> ..." (each post layer's
-        kernel); a weighted plan: "unfused weights=k_degree_w+k_agg_w" before those tokens.  A host query of the library's own dispatch (nothing is launched); raises
+        kernel); a weighted plan: "unfused weights=k_degree_w+k_agg_w" before those tokens; an
+        edge-featured plan: "unfused efeat=k_agg_e" before them.  A host query of the library's own dispatch (nothing is launched); raises
         where forward() would refuse the plan (XPG_FORWARD_STRICT=1)."""
         buf = ctypes.create_string_buffer(1024)
         name, lead = self._entry("xpg_forward_describe")

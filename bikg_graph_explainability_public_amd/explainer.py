@@ -73,7 +73,7 @@ def set_seed(seed=100):
 class Explainer:
     def __init__(self, feat, edge_index, arch, params, names, pathways=None, pathway_names=None,
                  element_type=None, problem="node_prediction", node_types=None,
-                 edge_types=None, edge_weight=None):
+                 edge_types=None, edge_weight=None, edge_attr=None):
         self.initial_assertions(feat, edge_index, arch, params, names, pathways, pathway_names,
                                 element_type, problem)
         self.feat = feat
@@ -88,12 +88,17 @@ class Explainer:
         self.node_types = node_types
         self.edge_types = edge_types
         self.edge_weight = edge_weight
+        self.edge_attr = edge_attr
         self.last_run = None  # diagnostics of the last run (per-repeat losses, path used)
         self.group = None     # torch.distributed process group for multi-GPU runs (None = world)
         self._verified = set()  # module states whose compiled program passed verify_plan
         self._queries = {}      # per-query (prepare context, plan, arch check): _query_key
+        if edge_weight is not None and edge_attr is not None:
+            raise NotImplementedError("edge_attr together with edge_weight is not supported")
         if edge_weight is not None:
             self._check_edge_weight()
+        if edge_attr is not None:
+            self._check_edge_attr()
         if self.pooled:
             if "graph" not in self.problem:
                 raise ValueError(f"arch.forward takes three parameters (x, edge_index, batch): that "
@@ -129,6 +134,33 @@ class Explainer:
             raise TypeError("edge_weight must be a torch tensor with one weight per edge")
         pipeline.require_edge_weight_arch(self.arch)
         pipeline.checked_edge_weight(self.arch, self.edge_weight, self.edge_index.shape[1])
+
+    def _check_edge_attr(self):
+        """`edge_attr` ([E, D] or [E] float tensor, one finite row per edge; PyG 2.0.4's edge_attr
+        of GINEConv): node_prediction and graph_prediction on homogeneous tensors.  The arch is
+        called `arch(x, edge_index[, batch], edge_attr=ea)` with each perturbed copy's kept edges'
+        rows; on the engine (GINEConv models) the plan carries them (k_agg_e)."""
+        if self.edge_weight is not None:
+            raise NotImplementedError("edge_attr together with edge_weight is not supported")
+        if isinstance(self.feat, dict) or isinstance(self.edge_index, dict):
+            raise NotImplementedError("edge_attr: homogeneous tensors only (no hetero dict graphs)")
+        if self.node_types is not None or self.edge_types is not None or self.element_type is not None:
+            raise NotImplementedError("edge_attr with node_types / edge_types is not supported")
+        if "edge" in self.problem or "link" in self.problem or bool(self.params.get("edge_masks", False)):
+            raise NotImplementedError("edge_attr under edge masks / link_prediction is not supported "
+                                      "(node_prediction and graph_prediction only)")
+        if not isinstance(self.edge_attr, torch.Tensor):
+            raise TypeError("edge_attr must be a torch tensor with one row per edge")
+        pipeline.require_edge_attr_arch(self.arch)
+        engine.check_edge_attr(self.edge_attr, self.edge_index.shape[1])
+
+    @staticmethod
+    def _edge_kw(c):
+        """The keyword every path of a prepared query hands on: the computational subgraph's edge
+        weights, its edge attribute rows, or nothing."""
+        if c.get("sub_w") is not None:
+            return {"edge_weight": c["sub_w"]}
+        return {"edge_attr": c["sub_a"]} if c.get("sub_a") is not None else {}
 
     @property
     def attention_engine(self):
@@ -245,7 +277,8 @@ class Explainer:
         return (id(self.arch), state[0], state[1], self.edge_masks, self.attention_engine,
                 bool(getattr(plan, "multi_type", False)),
                 tuple(c["h_ntypes"] or ()), tuple(c["h_etypes"] or ()),
-                tuple(getattr(plan, "lowering", ())), self.edge_weight is not None)
+                tuple(getattr(plan, "lowering", ())), self.edge_weight is not None,
+                self.edge_attr is not None)
 
     def _query_key(self, element, device):
         """The cache slot of a query: element, problem, device and modes.  Whether the slot's
@@ -254,7 +287,7 @@ class Explainer:
         stream as the reference's)."""
         return (str(element), type(element).__name__, self.problem, self.edge_masks, str(device),
                 _freeze(self.element_type), str(self.params.get("verify_arch", True)),
-                self.attention_engine, self.edge_weight is not None)
+                self.attention_engine, self.edge_weight is not None, self.edge_attr is not None)
 
     def _query_sources(self, params, bufs):
         """Identity snapshot of what prepare() and the query's ForwardPlan read: the graph and
@@ -263,7 +296,7 @@ class Explainer:
         pathways inputs and the module (identity), the module's parameters and buffers."""
         return _snapshot((self.feat, self.edge_index, self.node_types, self.edge_types,
                           self.names, self.pathways, self.pathway_names, self.arch,
-                          tuple(params), tuple(bufs), self.edge_weight))
+                          tuple(params), tuple(bufs), self.edge_weight, self.edge_attr))
 
     def _query_fingerprints(self):
         """Full-content fingerprints of the inputs read in full by prepare(): pathways and
@@ -312,7 +345,7 @@ class Explainer:
             if "bytes" not in e:
                 if user is None:
                     user = _tensor_ptrs((self.feat, self.edge_index, self.node_types, self.edge_types,
-                                         self.edge_weight))
+                                         self.edge_weight, self.edge_attr))
                 ctx = sum(t.numel() * t.element_size() for t in e["c"].values()
                           if isinstance(t, torch.Tensor) and t.data_ptr() not in user)
                 e["bytes"] = ctx + (e["plan"].device_bytes() if e["plan"] is not None else 0)
@@ -355,6 +388,11 @@ class Explainer:
         if self.edge_weight is not None:
             self._check_edge_weight()  # again: the tensor may have been edited in place
             ew = self.edge_weight.reshape(-1).to(device=device, dtype=torch.float32)
+        ea = sub_a = None
+        if self.edge_attr is not None:
+            self._check_edge_attr()  # again: the tensor may have been edited in place
+            ea = self.edge_attr.reshape(-1, 1) if self.edge_attr.dim() == 1 else self.edge_attr
+            ea = ea.to(device=device, dtype=torch.float32)
         if self.edge_masks:
             # edge problem, edge masks (non-compat: the reference's edge path is broken at
             # masks.py:294 and data.py:331): mask columns = the computational graph's edges
@@ -381,7 +419,11 @@ class Explainer:
             rels = len(h_etypes) if h_etypes is not None else 0
             n_hops = Model(self.arch).get_hops(rels)
             ind = self.extract_index(element, names)
-            if ew is not None:
+            if ea is not None:
+                sub_feat, sub_ei, sub_names, sub_ind, sub_nt, sub_et, pos, sub_a = data.comp_graph(
+                    ind, n_hops, self.problem, names, node_types, edge_types, return_pos=True,
+                    edge_attr=ea)
+            elif ew is not None:
                 sub_feat, sub_ei, sub_names, sub_ind, sub_nt, sub_et, pos, sub_w = data.comp_graph(
                     ind, n_hops, self.problem, names, node_types, edge_types, return_pos=True,
                     edge_weight=ew)
@@ -396,7 +438,7 @@ class Explainer:
             # writes to it, so the run reads the caller's tensors and names directly)
             sub_feat, sub_ei, sub_names = feat, ei, names
             ind = sub_ind = self.extract_index(element, sub_names)
-            sub_nt, sub_et, sub_w = node_types, edge_types, ew
+            sub_nt, sub_et, sub_w, sub_a = node_types, edge_types, ew, ea
             if pathways is not None:
                 sub_pw, sub_pw_names = pathways, pathway_names
         if "graph" not in self.problem and not self.edge_masks and (self.element_type is not None or
@@ -416,7 +458,7 @@ class Explainer:
         S = Data(sub_feat, sub_ei).element_size(self.problem)
         return {"link": link, "label_type": label_type, "sub_feat": sub_feat, "sub_ei": sub_ei,
                 "sub_names": sub_names, "sub_ind": sub_ind, "sub_nt": sub_nt, "sub_et": sub_et,
-                "sub_w": sub_w,
+                "sub_w": sub_w, "sub_a": sub_a,
                 "h_ntypes": h_ntypes, "h_etypes": h_etypes, "padded_dims": padded_dims, "sub_pw": sub_pw,
                 "sub_pw_names": sub_pw_names, "sub_pw_inds": sub_pw_inds, "S": S,
                 "has_pathways": pathways is not None, "ind": ind,
@@ -527,8 +569,9 @@ class Explainer:
         clock.mark("plan")
         # typed edge problems (nn.RelLinkModel): the subgraph's edge types and the query's own
         typed = {"edge_type": c["sub_et"], "label_type": c["label_type"]} if self.edge_masks else {}
-        # weighted graphs: the computational subgraph's edge weights, for every path
-        wkw = {"edge_weight": c["sub_w"]} if c.get("sub_w") is not None else {}
+        # weighted graphs / graphs with edge features: the computational subgraph's edge weights
+        # or attribute rows, for every path
+        wkw = self._edge_kw(c)
 
         if cached:
             plan, verify = cached[1], None
@@ -716,7 +759,7 @@ class Explainer:
         geo = (c["sub_nt"], c["sub_et"], c["h_ntypes"], c["h_etypes"], c["padded_dims"])
         Q = len(inds)
         assert len(set(inds)) == Q, "run_queries: duplicate query elements"
-        wkw = {"edge_weight": c["sub_w"]} if c.get("sub_w") is not None else {}
+        wkw = self._edge_kw(c)
         plan = pipeline.build_plan(self.arch, sub_feat, sub_ei, inds, *geo, module_state=mstate,
                                    attention=self.attention_engine, **wkw)
         assert plan is not None and not getattr(plan, "multi_type", False), \

@@ -24,16 +24,23 @@ class Model:
             hops //= num_relations
         return hops
 
-    def infer(self, feat, edge_index, node_types=None, edge_types=None, batch=None, edge_weight=None):
+    def infer(self, feat, edge_index, node_types=None, edge_types=None, batch=None, edge_weight=None,
+              edge_attr=None):
         """model.py:62-116 — call convention picked from the forward signature.  A forward of
         three parameters is a graph-level (pooled) model, called `arch(x, edge_index, batch)`:
         `batch` [n] gives each node's graph (the copy of the union graph it belongs to; None: one
         graph).  An edge-level model's (x, edge_index, edge_label_index) is not that form.
-        `edge_weight` ([E], one per edge of `edge_index`) is passed on as that keyword."""
-        names = [n for n in inspect.signature(self.arch.forward).parameters if n != "edge_weight"]
+        `edge_weight` ([E], one per edge of `edge_index`) is passed on as that keyword, and so is
+        `edge_attr` ([E, D]); not both."""
+        names = [n for n in inspect.signature(self.arch.forward).parameters
+                 if n not in ("edge_weight", "edge_attr")]
         nargs = len(names)
-        # the optional trailing edge_weight keyword is no part of the call convention
+        # the optional trailing edge_weight / edge_attr keywords are no part of the call convention
         kw = {} if edge_weight is None else {"edge_weight": edge_weight}
+        if edge_attr is not None:
+            if edge_weight is not None:
+                raise ValueError("edge_attr and edge_weight together are not supported")
+            kw = {"edge_attr": edge_attr}
         with torch.no_grad():
             if nargs == 2:
                 return self.arch(feat, edge_index, **kw)
@@ -41,6 +48,8 @@ class Model:
                 return self.arch(feat, edge_index, batch, **kw)
             if edge_weight is not None:
                 raise TypeError("edge_weight with the 4-argument (typed) call is not supported")
+            if edge_attr is not None:
+                raise TypeError("edge_attr with the 4-argument (typed) call is not supported")
             if nargs == 4 and node_types is not None and edge_types is not None:
                 return self.arch(feat, edge_index, node_types, edge_types)
         raise TypeError("arch.forward must take (x, edge_index), (x, edge_index, batch) or "

@@ -250,6 +250,52 @@ class GINConv(MessagePassing):
         return f"nn={self.nn}"
 
 
+class GINEConv(MessagePassing):
+    """GINEConv (PyG 2.0.4): nn((1 + eps) x_t + sum over in-edges (j -> t) of relu(x_j + e_jt)),
+    e = lin(edge_attr) with lin = Linear(edge_dim, in_channels) when `edge_dim` is given, else
+    the attribute rows themselves (their width must be x's).  No self-loops are added: a self-loop
+    and a duplicate edge are messages of their own, each with its own attribute row.  `eps` is a
+    buffer, or a parameter with train_eps.  The input width is read off the first Linear of `nn`
+    (its in_features / in_channels), as PyG does."""
+
+    def __init__(self, nn, eps=0.0, train_eps=False, edge_dim=None, **kwargs):
+        super().__init__()
+        self.nn = nn
+        self.initial_eps, self.aggr = float(eps), "add"
+        if train_eps:
+            self.eps = torch.nn.Parameter(torch.tensor([float(eps)]))
+        else:
+            self.register_buffer("eps", torch.tensor([float(eps)]))
+        self.lin = None
+        if edge_dim is not None:
+            first = nn[0] if isinstance(nn, torch.nn.Sequential) else nn
+            if hasattr(first, "in_features"):
+                in_channels = first.in_features
+            elif hasattr(first, "in_channels"):
+                in_channels = first.in_channels
+            else:
+                raise ValueError("Could not infer input channels from `nn`.")
+            self.lin = Linear(edge_dim, in_channels)
+
+    def forward(self, x, edge_index, edge_attr=None):
+        if edge_attr is None:
+            raise ValueError("GINEConv needs an edge_attr")
+        ea = edge_attr.reshape(-1, 1) if edge_attr.dim() == 1 else edge_attr
+        ea = ea.to(x.dtype)
+        if self.lin is not None:
+            ea = self.lin(ea)
+        if ea.size(-1) != x.size(-1):
+            raise ValueError("Node and edge feature dimensionalities do not match. Consider setting "
+                             "the 'edge_dim' attribute of 'GINEConv'")
+        ei = edge_index.long()
+        out = torch.zeros_like(x)
+        out.index_add_(0, ei[1], torch.relu(x[ei[0]] + ea))
+        return self.nn(out + (1 + self.eps) * x)
+
+    def extra_repr(self):
+        return f"nn={self.nn}"
+
+
 class GATConv(MessagePassing):
     """GATConv (PyG 2.0.4): h = x W (W_src / W_dst for bipartite inputs), attention
     softmax over each target's in-edges of leaky_relu(a_src . h_j + a_dst . h_i, 0.2), heads
@@ -485,21 +531,33 @@ class HeteroConv(nn.Module):
         return out
 
 
+def _edge_kwargs(edge_weight, edge_attr):
+    """The keyword a stack hands to every conv: edge_weight, edge_attr or none (not both)."""
+    if edge_weight is not None and edge_attr is not None:
+        raise ValueError("edge_attr and edge_weight together are not supported")
+    if edge_weight is not None:
+        return {"edge_weight": edge_weight}
+    return {} if edge_attr is None else {"edge_attr": edge_attr}
+
+
 class ConvStack(nn.Module):
     """Model family of the reference tests/notebooks (tests/test_utils.py:10-83,
     examples/toy_example-caseA.ipynb cell 9): `conv` = ModuleList[Conv, ReLU]*, `fc` =
     ModuleList[Linear, act]* ending in Sigmoid.  `kind` in {"gcn", "sage", "gat"} or one of the
     sum / max families "sage-add", "sage-max", "graphconv" (add), "graphconv-max" and "gin"
-    (GINConv over Sequential(Linear, ReLU, Linear)); `hetero_rels`
+    (GINConv over Sequential(Linear, ReLU, Linear)), or "gine" (GINEConv over the same MLP, with
+    `edge_dim` handed to it; forward then takes the edge attributes as `edge_attr=`); `hetero_rels`
     wraps each conv in HeteroConv over the given edge types (single node type).  "gat":
     GATConv layers with `heads[i]` concatenated heads of dims[i + 1] channels (default all 1), so
     layer i reads dims[i] * heads[i - 1] columns and the head reads dims[-1] * heads[-1].
     "gatv2": the same with GATv2Conv layers; `share_weights` is handed to them."""
 
     def __init__(self, kind, dims, fc_dims, hetero_rels=None, final_act="sigmoid", heads=None,
-                 add_self_loops=True, share_weights=False):
+                 add_self_loops=True, share_weights=False, edge_dim=None):
         super().__init__()
         n_conv = len(dims) - 1
+        if edge_dim is not None and kind != "gine":
+            raise ValueError("edge_dim applies to kind='gine' only")
         if kind in ("gat", "gatv2"):
             heads = [1] * n_conv if heads is None else [int(h) for h in heads]
             if len(heads) != n_conv:
@@ -525,6 +583,8 @@ class ConvStack(nn.Module):
                 "graphconv": GraphConv,
                 "graphconv-max": lambda i, o: GraphConv(i, o, aggr="max"),
                 "gin": lambda i, o: GINConv(nn.Sequential(Linear(i, o), nn.ReLU(), Linear(o, o))),
+                "gine": lambda i, o: GINEConv(nn.Sequential(Linear(i, o), nn.ReLU(), Linear(o, o)),
+                                              edge_dim=edge_dim),
             }
             if kind not in makers:
                 raise ValueError(f"unknown ConvStack kind {kind!r}")
@@ -549,10 +609,11 @@ class ConvStack(nn.Module):
                        else nn.ReLU())
         self.fc = nn.ModuleList(fcs)
 
-    def forward(self, x, edge_index, edge_weight=None):
+    def forward(self, x, edge_index, edge_weight=None, edge_attr=None):
+        kw = _edge_kwargs(edge_weight, edge_attr)
         for i, c in enumerate(self.conv):
             if i % 2 == 0:
-                x = c(x, edge_index) if edge_weight is None else c(x, edge_index, edge_weight=edge_weight)
+                x = c(x, edge_index, **kw)
             elif isinstance(x, dict):
                 x = {k: c(v) for k, v in x.items()}
             else:
@@ -573,18 +634,20 @@ class BlockStack(nn.Module):
 
     `kind`: every ConvStack kind.  `norm`: None, "batch" (torch.nn.BatchNorm1d(width)) or "layer"
     (torch.nn.LayerNorm(width)); `width` = dims[i + 1] * heads[i] for "gat" / "gatv2".  kind "gin"
-    with norm "batch" is the textbook GIN block GINConv(Sequential(Linear, BatchNorm1d, ReLU,
-    Linear)) with no norm after the conv; with norm "layer" the LayerNorm follows the conv.
+    (and "gine", with `edge_dim` and forward's `edge_attr=`) with norm "batch" is the textbook GIN
+    block GINConv(Sequential(Linear, BatchNorm1d, ReLU, Linear)) with no norm after the conv; with norm "layer" the LayerNorm follows the conv.
 
     The engine lowers this family by class name plus the `residual` attribute (program.compile_arch):
     BatchNorm in eval mode folds into the weights (a post-op affine after attention layers),
     LayerNorm and the skip are the layer's post-op (k_post in csrc/xpgnn.hip)."""
 
     def __init__(self, kind, dims, fc_dims, norm=None, residual=False, final_act="sigmoid", heads=None,
-                 add_self_loops=True, share_weights=False):
+                 add_self_loops=True, share_weights=False, edge_dim=None):
         super().__init__()
         if norm not in (None, "batch", "layer"):
             raise ValueError("BlockStack norm must be None, 'batch' or 'layer'")
+        if edge_dim is not None and kind != "gine":
+            raise ValueError("edge_dim applies to kind='gine' only")
         n_conv = len(dims) - 1
         attn = kind in ("gat", "gatv2")
         if attn:
@@ -600,6 +663,8 @@ class BlockStack(nn.Module):
         def gin(i, o):
             mlp = [Linear(i, o)] + ([nn.BatchNorm1d(o)] if norm == "batch" else []) + \
                 [nn.ReLU(), Linear(o, o)]
+            if kind == "gine":
+                return GINEConv(nn.Sequential(*mlp), edge_dim=edge_dim)
             return GINConv(nn.Sequential(*mlp))
         makers = {
             "gcn": GCNConv, "sage": SAGEConv,
@@ -607,12 +672,12 @@ class BlockStack(nn.Module):
             "sage-max": lambda i, o: SAGEConv(i, o, aggr="max"),
             "graphconv": GraphConv,
             "graphconv-max": lambda i, o: GraphConv(i, o, aggr="max"),
-            "gin": gin,
+            "gin": gin, "gine": gin,
         }
         if not attn and kind not in makers:
             raise ValueError(f"unknown BlockStack kind {kind!r}")
         convs = []
-        self.block_len = 2 + (norm is not None and not (kind == "gin" and norm == "batch"))
+        self.block_len = 2 + (norm is not None and not (kind in ("gin", "gine") and norm == "batch"))
         for i in range(n_conv):
             f_in, f_out = dims[i], dims[i + 1]
             if attn:
@@ -637,11 +702,11 @@ class BlockStack(nn.Module):
                        else nn.ReLU())
         self.fc = nn.ModuleList(fcs)
 
-    def forward(self, x, edge_index, edge_weight=None):
+    def forward(self, x, edge_index, edge_weight=None, edge_attr=None):
         n = self.block_len
+        kw = _edge_kwargs(edge_weight, edge_attr)
         for i in range(0, len(self.conv), n):
-            z = self.conv[i](x, edge_index) if edge_weight is None else \
-                self.conv[i](x, edge_index, edge_weight=edge_weight)
+            z = self.conv[i](x, edge_index, **kw)
             for m in self.conv[i + 1:i + n]:
                 z = m(z)
             x = z + x if self.residual and z.shape[-1] == x.shape[-1] else z
@@ -874,9 +939,8 @@ class PooledModel(nn.Module):
                        else nn.ReLU())
         self.fc = nn.ModuleList(fcs)
 
-    def forward(self, x, edge_index, batch=None, edge_weight=None):
-        h = self.encoder(x, edge_index) if edge_weight is None else \
-            self.encoder(x, edge_index, edge_weight=edge_weight)
+    def forward(self, x, edge_index, batch=None, edge_weight=None, edge_attr=None):
+        h = self.encoder(x, edge_index, **_edge_kwargs(edge_weight, edge_attr))
         h = global_pool(h, batch, self.pool)
         for layer in self.fc:
             h = layer(h)

@@ -70,7 +70,7 @@ def clear_programs():
 
 
 def compiled_program(arch, edge_type_names=None, node_type_names=None, state=None,
-                     attention=False, edge_weight=False):
+                     attention=False, edge_weight=False, edge_attr=False):
     """compile_arch(arch, ...) once per module state: keyed by the module (identity, checked by
     weak reference), every parameter and buffer (storage + in-place version counter: an
     optimizer step, load_state_dict or a replaced tensor compiles again) and the type names.
@@ -86,13 +86,13 @@ def compiled_program(arch, edge_type_names=None, node_type_names=None, state=Non
     key = (id(arch), state,
            tuple(tuple(e) for e in edge_type_names) if edge_type_names is not None else None,
            tuple(node_type_names) if node_type_names is not None else None, bool(attention),
-           bool(edge_weight))
+           bool(edge_weight), bool(edge_attr))
     hit = _PROGRAMS.get(key)
     if hit is not None and hit[0]() is arch:
         _PROGRAMS.move_to_end(key)
         return hit[1]
     prog = compile_arch(arch, edge_type_names, node_type_names, attention=bool(attention),
-                        edge_weight=bool(edge_weight))
+                        edge_weight=bool(edge_weight), edge_attr=bool(edge_attr))
     _PROGRAMS[key] = (weakref.ref(arch), prog)
     while len(_PROGRAMS) > 8:
         _PROGRAMS.popitem(last=False)
@@ -101,7 +101,7 @@ def compiled_program(arch, edge_type_names=None, node_type_names=None, state=Non
 
 def build_plan(arch, feat, edge_index, queries, node_type=None, edge_type=None,
                node_type_names=None, edge_type_names=None, padded_dims=None, module_state=None,
-               attention=False, edge_weight=None):
+               attention=False, edge_weight=None, edge_attr=None):
     """ForwardPlan for `arch` on the (sub)graph, or None when the engine cannot run it.
     `attention=True` (opt-in, Explainer params["attention_engine"]) also compiles GATConv
     relations, which otherwise run on the generic torch path.
@@ -119,7 +119,11 @@ def build_plan(arch, feat, edge_index, queries, node_type=None, edge_type=None,
     `edge_weight` ([E], one per edge of `edge_index`; homogeneous graphs): the arch is compiled
     for a weighted graph (GCNConv / GraphConv only) and the plan carries the weights.  A weight
     vector that is itself invalid (wrong length, not finite, negative with a GCNConv) raises
-    ValueError: no path could run it."""
+    ValueError: no path could run it.
+
+    `edge_attr` ([E, D] or [E], one row per edge of `edge_index`; homogeneous graphs): the arch is
+    compiled for a graph with edge features (GINEConv only) and the plan carries the rows.
+    Attributes that are themselves invalid (wrong row count, integer, not finite) raise ValueError."""
     multi = node_type_names is not None and node_type is not None and \
         len(torch.unique(node_type)) >= 2
     hetero = edge_type_names is not None and edge_type is not None
@@ -128,10 +132,18 @@ def build_plan(arch, feat, edge_index, queries, node_type=None, edge_type=None,
         if multi or hetero or node_type is not None or edge_type is not None:
             raise NotImplementedError("edge_weight on a heterogeneous (typed) graph is not supported")
         edge_weight = checked_edge_weight(arch, edge_weight, edge_index.shape[1])
+    if edge_attr is not None:
+        if edge_weight is not None:
+            raise NotImplementedError("edge_attr together with edge_weight is not supported")
+        require_edge_attr_arch(arch)
+        if multi or hetero or node_type is not None or edge_type is not None:
+            raise NotImplementedError("edge_attr on a heterogeneous (typed) graph is not supported")
+        edge_attr = engine.check_edge_attr(edge_attr, edge_index.shape[1])
     try:
         prog = compiled_program(arch, edge_type_names if hetero else None,
                                 node_type_names if multi else None, module_state,
-                                attention=attention, edge_weight=edge_weight is not None)
+                                attention=attention, edge_weight=edge_weight is not None,
+                                edge_attr=edge_attr is not None)
         check_rel_features(prog, feat)
     except UnsupportedArch as e:
         warnings.warn(f"engine cannot compile arch ({e}); using the generic torch path")
@@ -162,7 +174,8 @@ def build_plan(arch, feat, edge_index, queries, node_type=None, edge_type=None,
         else:
             rels = relation_edges(edge_index, edge_type if hetero else None,
                                   len(edge_type_names) if hetero else 1)
-        plan = engine.ForwardPlan(prog, x, rels, queries, node_type=nt, edge_weight=edge_weight)
+        plan = engine.ForwardPlan(prog, x, rels, queries, node_type=nt, edge_weight=edge_weight,
+                                  edge_attr=edge_attr)
     except ValueError as e:
         warnings.warn(f"engine plan rejected ({e}); using the generic torch path")
         return None
@@ -302,12 +315,12 @@ def multi_type_targets(y_rows, empty, batch, sub_ind, S, q4=True):
 def pooled_call(arch):
     """True for a graph-level model: a forward of three parameters (x, edge_index, batch), the
     form Model.infer calls with the union graph's copy index per node (nn.PooledModel).  An
-    optional `edge_weight` keyword is no part of the form."""
+    optional `edge_weight` or `edge_attr` keyword is no part of the form."""
     forward = getattr(arch, "forward", None)
     if forward is None:
         return False
     try:
-        names = [n for n in inspect.signature(forward).parameters if n != "edge_weight"]
+        names = [n for n in inspect.signature(forward).parameters if n not in ("edge_weight", "edge_attr")]
     except (TypeError, ValueError):
         return False
     return len(names) == 3 and names[2] != "edge_label_index"
@@ -333,16 +346,38 @@ def require_edge_weight_arch(arch):
                         "parameter: the model cannot be called on a weighted graph")
 
 
+def require_edge_attr_arch(arch):
+    """TypeError unless `arch.forward` has an `edge_attr` parameter (or takes **kwargs): the paths
+    of a graph with edge features call arch(x, edge_index[, batch], edge_attr=ea)."""
+    try:
+        ps = inspect.signature(arch.forward).parameters
+    except (TypeError, ValueError, AttributeError):
+        raise TypeError("edge_attr given, but arch.forward has no readable signature")
+    if "edge_attr" not in ps and not any(p.kind == p.VAR_KEYWORD for p in ps.values()):
+        raise TypeError(f"edge_attr given, but {type(arch).__name__}.forward has no edge_attr "
+                        "parameter: the model cannot be called on a graph with edge features")
+
+
 def generic_outputs(arch, feat, edge_index, mask, element_index, problem, node_type=None,
                     edge_type=None, node_type_names=None, edge_type_names=None,
-                    padded_dims=None, batch=None, q4=True, edge_weight=None):
+                    padded_dims=None, batch=None, q4=True, edge_weight=None, edge_attr=None):
     """wlm.py:349-436 semantics per batch of mask rows with the user's module in torch.
     Returns y [R] (the regression target of each row; for multi-node-type graphs the
     reference's output[ind::S] collapse, quirk Q4, broadcast over its batch).  A list of
     element indices (single-node-type graphs) returns y [R, Q]: every query's extraction from
     the same union-graph forward.  `edge_weight` ([E], homogeneous graphs): each copy's kept
-    edges carry their weights, `arch(x, edge_index[, batch], edge_weight=w)`."""
+    edges carry their weights, `arch(x, edge_index[, batch], edge_weight=w)`.  `edge_attr` ([E, D],
+    homogeneous graphs): they carry their attribute rows, `arch(..., edge_attr=ea)`."""
     pooled = pooled_call(arch)
+    if edge_attr is not None:
+        if edge_weight is not None:
+            raise NotImplementedError("edge_attr together with edge_weight is not supported")
+        require_edge_attr_arch(arch)
+        if node_type is not None or edge_type is not None:
+            raise NotImplementedError("edge_attr on a heterogeneous (typed) graph is not supported")
+        edge_attr = torch.as_tensor(edge_attr)
+        edge_attr = (edge_attr.reshape(-1, 1) if edge_attr.dim() == 1 else edge_attr).to(
+            device=mask.device, dtype=torch.float32)
     if edge_weight is not None:
         require_edge_weight_arch(arch)
         if node_type is not None or edge_type is not None:
@@ -353,7 +388,7 @@ def generic_outputs(arch, feat, edge_index, mask, element_index, problem, node_t
             raise ValueError("a pooled (graph-level) model has one output per graph: no query list")
         return _generic_multi(arch, feat, edge_index, mask, element_index, problem, node_type,
                               edge_type, node_type_names, edge_type_names, padded_dims, batch,
-                              edge_weight)
+                              edge_weight, edge_attr)
     data = Data(feat, edge_index)
     mc = Model(arch)
     R, S = mask.shape
@@ -362,8 +397,10 @@ def generic_outputs(arch, feat, edge_index, mask, element_index, problem, node_t
     for r0 in range(0, R, batch):
         mb = mask[r0:r0 + batch]
         B = mb.shape[0]
-        pew = None
-        if edge_weight is not None:
+        pew = pea = None
+        if edge_attr is not None:
+            cf, cnt, pei, pet, pea = data.perturbator(mb, problem, node_type, edge_type, edge_attr=edge_attr)
+        elif edge_weight is not None:
             cf, cnt, pei, pet, pew = data.perturbator(mb, problem, node_type, edge_type, edge_weight)
         else:
             cf, cnt, pei, pet = data.perturbator(mb, problem, node_type, edge_type)
@@ -378,13 +415,13 @@ def generic_outputs(arch, feat, edge_index, mask, element_index, problem, node_t
             # removed), one output row per copy; column out_col (0) is the regression target
             # (cf is a dict for a single-node-type graph with type names: the device is the mask's)
             gb = torch.arange(B, device=mb.device).repeat_interleave(S)
-            out = mc.infer(cf, pei, batch=gb, edge_weight=pew)
+            out = mc.infer(cf, pei, batch=gb, edge_weight=pew, edge_attr=pea)
             if out.dim() != 2 or out.shape[0] != B:
                 raise RuntimeError(f"a pooled model must return [{B}, out], got {tuple(out.shape)}")
             ys.append(out[:, 0].reshape(-1).float())
             continue
         if n_types < 2:
-            out = mc.infer(cf, pei, cnt, pet, edge_weight=pew)
+            out = mc.infer(cf, pei, cnt, pet, edge_weight=pew, edge_attr=pea)
         else:
             # one arch call over the disjoint union per node type (§8f2); HETERO_BATCHED =
             # False restores the reference's per-copy loop
@@ -413,7 +450,8 @@ def generic_outputs(arch, feat, edge_index, mask, element_index, problem, node_t
 
 
 def _generic_multi(arch, feat, edge_index, mask, queries, problem, node_type, edge_type,
-                   node_type_names, edge_type_names, padded_dims, batch, edge_weight=None):
+                   node_type_names, edge_type_names, padded_dims, batch, edge_weight=None,
+                   edge_attr=None):
     """generic_outputs for several queries of a single-node-type graph: [R, Q]."""
     data = Data(feat, edge_index)
     mc = Model(arch)
@@ -423,8 +461,10 @@ def _generic_multi(arch, feat, edge_index, mask, queries, problem, node_type, ed
     for r0 in range(0, R, batch):
         mb = mask[r0:r0 + batch]
         B = mb.shape[0]
-        pew = None
-        if edge_weight is not None:
+        pew = pea = None
+        if edge_attr is not None:
+            cf, cnt, pei, pet, pea = data.perturbator(mb, problem, node_type, edge_type, edge_attr=edge_attr)
+        elif edge_weight is not None:
             cf, cnt, pei, pet, pew = data.perturbator(mb, problem, node_type, edge_type, edge_weight)
         else:
             cf, cnt, pei, pet = data.perturbator(mb, problem, node_type, edge_type)
@@ -433,7 +473,7 @@ def _generic_multi(arch, feat, edge_index, mask, queries, problem, node_type, ed
                 and edge_type_names is not None:
             cf = data.homo2hetero(cf, cnt, node_type_names, padded_dims)
             pei = data.homo2hetero(pei, pet, edge_type_names)
-        out = mc.infer(cf, pei, cnt, pet, edge_weight=pew)
+        out = mc.infer(cf, pei, cnt, pet, edge_weight=pew, edge_attr=pea)
         if isinstance(out, dict):
             out, _ = mc.hetero2homo_output(out)
         ys.append(torch.stack([mc.extract_node_edge_output(out, int(q), S).reshape(-1).float()
@@ -443,7 +483,7 @@ def _generic_multi(arch, feat, edge_index, mask, queries, problem, node_type, ed
 
 def verify_plan(plan, arch, feat, edge_index, query, node_type=None, edge_type=None,
                 node_type_names=None, edge_type_names=None, padded_dims=None, rows=8, tol=1e-4,
-                edge_weight=None):
+                edge_weight=None, edge_attr=None):
     """Check the compiled program against the user's module on a few random masks (guards the
     registration-order lowering in program.compile_arch).  `query` may be the list of a
     multi-query plan's queries: every output column is then checked."""
@@ -456,13 +496,13 @@ def verify_plan(plan, arch, feat, edge_index, query, node_type=None, edge_type=N
         assert not multi, "multi-query plans are single-node-type"
         ref = generic_outputs(arch, feat, edge_index, mask, list(query), "node", node_type,
                               edge_type, node_type_names, edge_type_names, padded_dims,
-                              edge_weight=edge_weight)
+                              edge_weight=edge_weight, edge_attr=edge_attr)
         got = plan.forward(engine.pack_masks(mask))[:, :len(query)]
         err = (ref - got).abs().max().item()
         return err <= tol * max(1.0, ref.abs().max().item()), err
     ref = generic_outputs(arch, feat, edge_index, mask, query, "node", node_type, edge_type,
                           node_type_names, edge_type_names, padded_dims, q4=not multi,
-                          edge_weight=edge_weight)
+                          edge_weight=edge_weight, edge_attr=edge_attr)
     bits = engine.pack_masks(mask)
     got = plan.forward(bits)[:, 0]
     if multi:  # per-copy outputs on both sides (zero for copies without edges)

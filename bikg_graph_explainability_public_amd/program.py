@@ -67,6 +67,11 @@ class Term:
     norm: str = "mean"
     slices: int = 0
     coef: Optional[torch.Tensor] = None        # [num_relations, slices]
+    # kind "sum" of a GINEConv (PyG 2.0.4; programs marked `edge_featured`): the messages are
+    # relu(x_j + e_ji) with e = edge_attr edge_lin_w^T + edge_lin_b (GINEConv.lin; both None with
+    # edge_dim=None: the attribute rows themselves, of the layer's input width)
+    edge_lin_w: Optional[torch.Tensor] = None  # [f_in, D]
+    edge_lin_b: Optional[torch.Tensor] = None  # [f_in]
 
 
 @dataclass
@@ -121,6 +126,9 @@ class ModelProgram:
     # compiled for a weighted graph (compile_arch(edge_weight=True)): every conv is a GCNConv or a
     # GraphConv, the two convs of PyG 2.0.4 that take an edge_weight; the plan then needs the weights
     weighted: bool = False
+    # compiled for a graph with edge features (compile_arch(edge_attr=True)): every conv is a
+    # GINEConv; the plan then needs the attribute rows
+    edge_featured: bool = False
 
     @property
     def hops(self):
@@ -165,6 +173,10 @@ def _is_gin(m):
     return type(m).__name__ == "GINConv" and hasattr(m, "nn") and hasattr(m, "eps")
 
 
+def _is_gine(m):
+    return type(m).__name__ == "GINEConv" and hasattr(m, "nn") and hasattr(m, "eps") and hasattr(m, "lin")
+
+
 _RGCN_NAMES = ("RGCNConv", "FastRGCNConv")
 
 
@@ -174,7 +186,7 @@ def _is_rgcn(m):
 
 def _is_conv(m, attention=False):
     return type(m).__name__ in ("GCNConv", "SAGEConv", "HeteroConv") or _is_graphconv(m) or _is_gin(m) \
-        or _is_rgcn(m) or (attention and (_is_gat(m) or _is_gatv2(m)))
+        or _is_gine(m) or _is_rgcn(m) or (attention and (_is_gat(m) or _is_gatv2(m)))
 
 
 def _is_linear(m):
@@ -444,6 +456,23 @@ def _gin_terms(conv, rel):
     return [Term("sum", rel, W)], b, root, W.shape[1], W.shape[0], extra
 
 
+def _gine_terms(conv, rel):
+    """GINEConv: _gin_terms' lowering (the same MLP shapes, root and BatchNorm folds); the "sum"
+    term carries the edge map GINEConv.lin (None with edge_dim=None)."""
+    out = _gin_terms(conv, rel)
+    term, f_in = out[0][0], out[3]
+    lin = getattr(conv, "lin", None)
+    if lin is not None:
+        if _lazy(lin):
+            raise UnsupportedArch("GINEConv.lin with uninitialised (lazy) weights")
+        w = _f32(lin.weight)
+        if w.dim() != 2 or w.shape[0] != f_in:
+            raise UnsupportedArch(f"GINEConv.lin of {tuple(w.shape)} on an input of width {f_in}")
+        term.edge_lin_w = w
+        term.edge_lin_b = _f32(lin.bias) if getattr(lin, "bias", None) is not None else torch.zeros(f_in)
+    return out
+
+
 _REL_NORM = {"mean": "mean", "add": "sum", "sum": "sum"}
 
 
@@ -537,6 +566,8 @@ def _single_conv_terms(conv, rel, attention=False, bipartite=False):
         W = _f32(conv.lin_rel.weight)
         b = _f32(conv.lin_rel.bias) if getattr(conv.lin_rel, "bias", None) is not None else None
         return [Term(kind, rel, W)], b, _f32(conv.lin_root.weight), W.shape[1], W.shape[0]
+    if _is_gine(conv):
+        raise UnsupportedArch("GINEConv inside HeteroConv")
     if _is_gin(conv):
         t, b, root, f_in, f_out, extra = _gin_terms(conv, rel)
         if extra is not None:
@@ -578,8 +609,8 @@ def _conv_layer(conv, rel_index, attention=False):
     else:
         if rel_index is not None and len(rel_index) != 1:
             raise UnsupportedArch("homogeneous conv on a multi-relation graph")
-        if _is_gin(conv):
-            terms, bias, root, f_in, f_out, extra = _gin_terms(conv, 0)
+        if _is_gin(conv) or _is_gine(conv):
+            terms, bias, root, f_in, f_out, extra = (_gine_terms if _is_gine(conv) else _gin_terms)(conv, 0)
             if extra is not None:
                 terms.append(Term("root", -1, root))
                 return terms, (torch.zeros(f_out) if bias is None else bias), f_in, f_out, extra
@@ -696,7 +727,8 @@ def _check_widths(prog):
 POOL_KIND = {"mean": "mean", "add": "sum", "sum": "sum", "max": "max"}
 
 
-def _compile_pooled(arch, edge_type_names, node_type_names, attention, edge_weight=False):
+def _compile_pooled(arch, edge_type_names, node_type_names, attention, edge_weight=False,
+                    edge_attr=False):
     """nn.PooledModel (matched by class name + `encoder`, `pool`, `fc`): the encoder's conv
     layers, the readout, then the Linear / activation units of `fc` as the head."""
     pool = arch.pool
@@ -704,7 +736,8 @@ def _compile_pooled(arch, edge_type_names, node_type_names, attention, edge_weig
         raise UnsupportedArch(f"PooledModel(pool={pool!r})")
     if node_type_names is not None and len(node_type_names) >= 2:
         raise UnsupportedArch("PooledModel on a multi-node-type graph")
-    prog = compile_arch(arch.encoder, edge_type_names, node_type_names, attention, edge_weight)
+    prog = compile_arch(arch.encoder, edge_type_names, node_type_names, attention, edge_weight,
+                        edge_attr)
     if prog.link_act is not None:
         raise UnsupportedArch("PooledModel over an edge-level (link) encoder")
     if prog.pool is not None:
@@ -727,7 +760,7 @@ def _compile_pooled(arch, edge_type_names, node_type_names, attention, edge_weig
 
 
 def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
-                 attention=False, edge_weight=False) -> ModelProgram:
+                 attention=False, edge_weight=False, edge_attr=False) -> ModelProgram:
     """Lower `arch` to a ModelProgram.  `edge_type_names` (list of (src, rel, dst) tuples in
     homogenised edge-type order, data.py:743-822) enables HeteroConv relations;
     `node_type_names` with two or more types selects the multi-node-type lowering.
@@ -735,7 +768,18 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
     relations, to "att2" terms; by default an arch with either raises UnsupportedArch.
     `edge_weight=True`: the arch will be called with an edge_weight.  Only GCNConv and GraphConv take
     one in PyG 2.0.4, so every conv must be one of the two (inside a ConvStack, a BlockStack or a
-    PooledModel encoder alike); the program is marked `weighted`."""
+    PooledModel encoder alike); the program is marked `weighted`.
+    `edge_attr=True`: the arch will be called with an edge_attr.  Every conv must be a GINEConv (the
+    same three containers); the program is marked `edge_featured` and its "sum" terms carry the
+    convs' edge maps.  Without the flag a GINEConv raises UnsupportedArch: it cannot run without
+    its attributes."""
+    if edge_attr:
+        if edge_weight:
+            raise UnsupportedArch("edge_attr together with edge_weight")
+        if type(arch).__name__ in ("LinkModel", "RelLinkModel"):
+            raise UnsupportedArch("edge_attr with an edge-level (link) model")
+        if edge_type_names is not None or node_type_names is not None:
+            raise UnsupportedArch("edge_attr on a heterogeneous (typed) graph")
     if edge_weight:
         if type(arch).__name__ in ("LinkModel", "RelLinkModel"):
             raise UnsupportedArch("edge_weight with an edge-level (link) model")
@@ -764,7 +808,7 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
             prog.link_rel = _f32(emb)
         return prog
     if type(arch).__name__ == "PooledModel" and all(hasattr(arch, a) for a in ("encoder", "pool", "fc")):
-        return _compile_pooled(arch, edge_type_names, node_type_names, attention, edge_weight)
+        return _compile_pooled(arch, edge_type_names, node_type_names, attention, edge_weight, edge_attr)
     rel_index = None
     if edge_type_names is not None:
         rel_index = {tuple(et): i for i, et in enumerate(edge_type_names)}
@@ -780,6 +824,10 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
         if edge_weight and not (type(units[i]).__name__ == "GCNConv" or _is_graphconv(units[i])):
             raise UnsupportedArch(f"{type(units[i]).__name__} takes no edge_weight (GCNConv and "
                                   "GraphConv do)")
+        if edge_attr and not _is_gine(units[i]):
+            raise UnsupportedArch(f"{type(units[i]).__name__} takes no edge_attr (GINEConv does)")
+        if _is_gine(units[i]) and not edge_attr:
+            raise UnsupportedArch("GINEConv needs edge_attr")
         if multi:
             terms, bias, f_in, f_out, prog.out_type = _conv_layer_multi(
                 units[i], rel_index, list(node_type_names), attention)
@@ -824,6 +872,7 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
     if type(arch).__name__ == "BlockStack" and getattr(arch, "residual", False):
         _add_residuals(prog)
     prog.weighted = bool(edge_weight)
+    prog.edge_featured = bool(edge_attr)
     return prog
 
 
@@ -850,6 +899,6 @@ def count_message_passing(arch: nn.Module) -> int:
     for m in arch.modules():
         if any(c.__name__ == "MessagePassing" for c in type(m).__mro__):
             n += 1
-        elif type(m).__name__ in ("GCNConv", "SAGEConv", "GATConv", "GATv2Conv", "GINConv", "GraphConv") + _RGCN_NAMES:
+        elif type(m).__name__ in ("GCNConv", "SAGEConv", "GATConv", "GATv2Conv", "GINConv", "GINEConv", "GraphConv") + _RGCN_NAMES:
             n += 1
     return n

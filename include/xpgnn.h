@@ -42,7 +42,9 @@
  *                                        max readout and a dense head, one output per mask row;
  *                                        XPG_TERM_ATT2 = 7: GATv2Conv layers, enum xpg_term below;
  *                                        xpg_masked_forward_w: the same with PyG's edge_weight of
- *                                        GCNConv / GraphConv, struct xpg_edge_weights below)
+ *                                        GCNConv / GraphConv, struct xpg_edge_weights below;
+ *                                        xpg_masked_forward_e: the same with PyG's edge_attr of
+ *                                        GINEConv, struct xpg_edge_feats below)
  *   xpg_pool_rows / _workspace / _describe — the readout alone (PyG global_mean_pool /
  *                                        global_add_pool / global_max_pool over one graph per row)
  *   xpg_forward_describe / xpg_wide_variants — none: host queries of xpg_masked_forward's own
@@ -584,6 +586,52 @@ int xpg_masked_forward_w(const xpg_forward_plan* plan, const xpg_post_desc* post
                          void* workspace, size_t workspace_bytes, xpg_stream_t stream);
 int xpg_forward_describe_w(const xpg_forward_plan* plan, const xpg_post_desc* post,
                            const xpg_edge_weights* weights, int64_t rows, char* buf, size_t n);
+
+/* Edge features (v27 addendum: new symbols only; the version, every struct above and every entry
+ * point above are unchanged).  One finite float row per edge of the graph (PyG 2.0.4's `edge_attr`
+ * of GINEConv), already mapped to each conv layer's input width (E_l = lin_l(edge_attr), or the
+ * rows themselves) and gathered into the plan's CSR orders, all device arrays of f_in_pad floats
+ * per row with zero padded columns.  feats == NULL: each _e entry point is its _w namesake, same
+ * results (the _w entry points are that case of the same code).  Node masks as ever: in mask row b
+ * an edge (j -> t) survives iff bit(b, j) & bit(b, t); no self-loop is added, and a self-loop or a
+ * duplicate edge is a message of its own with its own row.
+ *   SUM term:  out[t] = sum over t's self-loops k of relu(x[t] + self_e[k])
+ *                     + sum over kept in-edges e = (j -> t), in CSR order, of relu(x[j] + agg_e[e])
+ *              for a kept t, 0 for a masked-out one.  ROOT terms (which carry GINEConv's (1 + eps)
+ *              fold), post-ops, the pooled readout and the head are unchanged.
+ * Every layer runs in the aggregate-then-transform form (layer 1: the raw form, weight and
+ * f_in_pad set, every term's table the one X[F_0] table).  A SUM layer's descriptor must set
+ * self_ptr (agg_eid / self_eid are not read): self_e's row k belongs to entry k of the self-loop
+ * CSR, agg_e's row e to entry e of agg_src / agg_f0.  Layer 1 may also give msg_rows
+ * [n_edges + n_self][f_in_pad]: relu(x[j] + agg_e[e]) per in-edge, then relu(x[t] + self_e[k]) per
+ * self-loop, formed in fp32 (its sources are feature rows shared by every mask row); the kernel
+ * then loads that one row per edge and adds the same values (XPG_EFEAT_MSG=0: ignored, for
+ * diagnostics).  k_agg_e<MSG, LPS, NV> is k_agg_w's item / lane mapping.
+ * Host checks, XPG_EINVAL before any launch: weights given as well; edge_masks or edge_dot;
+ * n_rel > 1; tgt_type; a term kind other than SUM / ROOT; a layer in the table form; a missing
+ * array (layers; self_ptr, agg_e, self_e of a layer with a SUM term; a ROOT-only layer's record is
+ * not read); msg_rows past layer 1.  An edge-featured plan runs on the multi-kernel path only (a
+ * forced rows / fused / wide path under XPG_FORWARD_STRICT=1 is refused).
+ * xpg_forward_describe_e writes `unfused efeat=k_agg_e`, then the ` post<l>=...` tokens.  The
+ * workspace is that of the same plan without features on the multi-kernel path. */
+typedef struct xpg_layer_efeat {
+  const float* agg_e;     /* [n_edges][f_in_pad] edge row of in-edge e (the index of agg_f0)     */
+  const float* self_e;    /* [n_self][f_in_pad] edge row of self-loop k (the index of self_eid)  */
+  const float* msg_rows;  /* layer 1, optional: [n_edges + n_self][f_in_pad] whole messages      */
+} xpg_layer_efeat;
+typedef struct xpg_edge_feats {
+  const xpg_layer_efeat* layers; /* host array [n_layers]                                       */
+} xpg_edge_feats;
+int xpg_forward_workspace_e(const xpg_forward_plan* plan, const xpg_post_desc* post,
+                            const xpg_edge_weights* weights, const xpg_edge_feats* feats,
+                            int64_t rows, size_t* bytes);
+int xpg_masked_forward_e(const xpg_forward_plan* plan, const xpg_post_desc* post,
+                         const xpg_edge_weights* weights, const xpg_edge_feats* feats,
+                         const uint32_t* bits, int64_t rows, float* y, void* workspace,
+                         size_t workspace_bytes, xpg_stream_t stream);
+int xpg_forward_describe_e(const xpg_forward_plan* plan, const xpg_post_desc* post,
+                           const xpg_edge_weights* weights, const xpg_edge_feats* feats,
+                           int64_t rows, char* buf, size_t n);
 
 /* Optional per-kernel timing of xpg_masked_forward's wide (full-graph) path (v13): with profiling
  * on, every launch of a profiled kernel is bracketed by two hipEvents on its stream;
