@@ -19,6 +19,7 @@ TERM = {"gcn": 0, "mean": 1, "root": 2, "att": 3, "sum": 4, "max": 5, "rel": 6, 
 REL_NORM = {"mean": 0, "sum": 1}
 POOL = {None: 0, "mean": 1, "sum": 2, "max": 3}
 NORM = {None: 0, "layer": 1}
+CLASS_KIND = {None: 0, "softmax": 1, "log_softmax": 2}
 
 c_i32, c_i64, c_f32, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
@@ -90,6 +91,11 @@ class EdgeFeats(ctypes.Structure):
     _fields_ = [("layers", ctypes.POINTER(LayerEfeat))]
 
 
+class ClassOut(ctypes.Structure):
+    """xpg_class_out (v27 addendum): the class readout; col = -1 asks for every class."""
+    _fields_ = [("kind", c_i32), ("col", c_i32)]
+
+
 class WlmParams(ctypes.Structure):
     _fields_ = [("lr", c_f32), ("l1_lambda", c_f32), ("beta1", c_f32), ("beta2", c_f32),
                 ("eps", c_f32), ("weight_decay", c_f32)]
@@ -154,6 +160,16 @@ _SIGS = {
     "xpg_forward_describe_e": ([ctypes.POINTER(ForwardPlanDesc), ctypes.POINTER(PostDesc),
                                 ctypes.POINTER(EdgeWeights), ctypes.POINTER(EdgeFeats), c_i64, ctypes.c_char_p,
                                 ctypes.c_size_t], c_i32),
+    "xpg_forward_workspace_c": ([ctypes.POINTER(ForwardPlanDesc), ctypes.POINTER(PostDesc),
+                                 ctypes.POINTER(EdgeWeights), ctypes.POINTER(EdgeFeats),
+                                 ctypes.POINTER(ClassOut), c_i64, ctypes.POINTER(ctypes.c_size_t)], c_i32),
+    "xpg_masked_forward_c": ([ctypes.POINTER(ForwardPlanDesc), ctypes.POINTER(PostDesc),
+                              ctypes.POINTER(EdgeWeights), ctypes.POINTER(EdgeFeats), ctypes.POINTER(ClassOut),
+                              c_vp, c_i64, c_vp, c_vp, ctypes.c_size_t, c_vp], c_i32),
+    "xpg_forward_describe_c": ([ctypes.POINTER(ForwardPlanDesc), ctypes.POINTER(PostDesc),
+                                ctypes.POINTER(EdgeWeights), ctypes.POINTER(EdgeFeats), ctypes.POINTER(ClassOut),
+                                c_i64, ctypes.c_char_p, ctypes.c_size_t], c_i32),
+    "xpg_class_out_rows": ([c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp], c_i32),
     "xpg_post_rows": ([c_vp, c_i64, c_i64, c_i64, ctypes.POINTER(PostDesc), c_vp, c_i64, c_i64, c_i64,
                        c_vp, c_vp], c_i32),
     "xpg_post_describe": ([c_i64, c_i64, c_i64, ctypes.POINTER(PostDesc), ctypes.c_char_p,

@@ -6876,8 +6876,148 @@ int launch_post(float* h, int64_t M, int64_t ld, int64_t f_out, const xpg_post_d
   return XPG_OK;
 }
 
+// ------------------------------------------------------------------------------------ class readout
+// The class readout of a classifier (xpg_class_out, xpg_class_out_rows; the rules are in xpgnn.h):
+// z [M][ld] -> column c of every row (ALL = false, y [M]) or all n_real columns (ALL = true,
+// y [M][n_real] row-major), after none / softmax / log_softmax over the n_real real columns.  The
+// item and lane mapping are k_post's: one row on a group of G lanes, G the power of two >= ld / 4,
+// lane c holding the row's float4 chunk c.  The maximum and the sum of exp(z - max) each cross the
+// group by one xor butterfly (max and + commute, so every lane of a group ends with the same bits,
+// reduced in an order that depends on (n_real, ld) alone); columns past n_real are never read as
+// values: they give -inf to the maximum and 0 to the sum.  No LDS, no atomics.  Every lane of a
+// wave stays in the loop and rows past M are masked, so each shuffle reads a live lane.
+struct ClassArgs {
+  const float* z;
+  int64_t M;
+  int ld, n_real, group, col;  // col: the class of ALL = false
+  float* y;
+};
+
+template <int KIND, bool ALL>
+__global__ __launch_bounds__(64 * kPostWaves) void k_class_out(const ClassArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int per_wave = 64 / a.group;
+  const int c = lane & (a.group - 1);
+  const int col = 4 * c;
+  const bool chunk = col < a.ld;
+  const int64_t per_block = (int64_t)kPostWaves * per_wave;
+  const bool r0 = col < a.n_real, r1 = col + 1 < a.n_real, r2 = col + 2 < a.n_real, r3 = col + 3 < a.n_real;
+  const int sel = a.col - col;  // ALL = false: 0..3 on the one lane of the group that holds the class
+  const float ninf = -__builtin_inff();
+  for (int64_t base = (int64_t)blockIdx.x * per_block; base < a.M; base += (int64_t)gridDim.x * per_block) {
+    const int64_t m = base + wave * per_wave + lane / a.group;
+    const bool live = chunk && m < a.M;
+    const float4 in = live ? *reinterpret_cast<const float4*>(a.z + m * a.ld + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+    float v0 = in.x, v1 = in.y, v2 = in.z, v3 = in.w;
+    if (KIND != XPG_CLASS_NONE) {
+      float mx = fmaxf(fmaxf(r0 ? v0 : ninf, r1 ? v1 : ninf), fmaxf(r2 ? v2 : ninf, r3 ? v3 : ninf));
+      for (int s = 1; s < a.group; s <<= 1) mx = fmaxf(mx, __shfl_xor(mx, s, 64));
+      // (a row past M computes on zeros and stores nothing)
+      const float d0 = v0 - mx, d1 = v1 - mx, d2 = v2 - mx, d3 = v3 - mx;
+      const float e0 = r0 ? expf(d0) : 0.f, e1 = r1 ? expf(d1) : 0.f;
+      const float e2 = r2 ? expf(d2) : 0.f, e3 = r3 ? expf(d3) : 0.f;
+      const float sum = post_group_sum((e0 + e1) + (e2 + e3), a.group);
+      if (KIND == XPG_CLASS_SOFTMAX) {
+        v0 = e0 / sum;
+        v1 = e1 / sum;
+        v2 = e2 / sum;
+        v3 = e3 / sum;
+      } else {
+        const float ls = logf(sum);
+        v0 = d0 - ls;
+        v1 = d1 - ls;
+        v2 = d2 - ls;
+        v3 = d3 - ls;
+      }
+    }
+    if (!live) continue;
+    if (ALL) {  // the lanes that hold the chunks store them: consecutive floats across the group
+      float* yr = a.y + m * a.n_real + col;
+      if (r0) yr[0] = v0;
+      if (r1) yr[1] = v1;
+      if (r2) yr[2] = v2;
+      if (r3) yr[3] = v3;
+    } else if (sel >= 0 && sel < 4) {
+      a.y[m] = sel == 0 ? v0 : (sel == 1 ? v1 : (sel == 2 ? v2 : v3));
+    }
+  }
+}
+
+const char* class_kernel_name(int kind, bool all) {
+  static const char* const names[] = {"k_class_out<none,one>",        "k_class_out<none,all>",
+                                      "k_class_out<softmax,one>",     "k_class_out<softmax,all>",
+                                      "k_class_out<log_softmax,one>", "k_class_out<log_softmax,all>"};
+  return names[2 * kind + (all ? 1 : 0)];
+}
+// the checks of a class readout that need no plan (xpg_class_out_rows and class_plan_check share them)
+int class_shape_check(int64_t ld, int64_t n_real, int kind, int col) {
+  XPG_REQ(kind >= XPG_CLASS_NONE && kind <= XPG_CLASS_LOG_SOFTMAX, "class_out: kind outside enum xpg_class_kind");
+  XPG_REQ(ld >= 4 && ld <= 256 && ld % 4 == 0, "class_out: ld must be a multiple of 4 in 4..256");
+  XPG_REQ(n_real >= 1 && n_real <= ld, "class_out: 1 <= n_real <= ld required");
+  XPG_REQ(col >= -1 && col < n_real, "class_out: col outside [-1, n_real)");
+  return XPG_OK;
+}
+
+int launch_class_out(const float* z, int64_t M, int64_t ld, int64_t n_real, int kind, int col, float* y,
+                     hipStream_t st) {
+  if (const int rc = class_shape_check(ld, n_real, kind, col)) return rc;
+  XPG_REQ(M >= 0 && M <= (int64_t(1) << 40), "class_out: M out of range");
+  if (M == 0) return XPG_OK;
+  XPG_REQ(z && reinterpret_cast<uintptr_t>(z) % 16 == 0, "class_out: in must be non-null and 16-byte aligned");
+  XPG_REQ(y && reinterpret_cast<uintptr_t>(y) % 4 == 0, "class_out: out must be non-null and 4-byte aligned");
+  ClassArgs a;
+  a.z = z;
+  a.M = M;
+  a.ld = static_cast<int>(ld);
+  a.n_real = static_cast<int>(n_real);
+  a.group = post_group(ld);
+  a.col = col;
+  a.y = y;
+  const int64_t per_block = (int64_t)kPostWaves * (64 / a.group);
+  const dim3 grid(static_cast<unsigned>(std::min<int64_t>(cdiv(M, per_block), 1 << 20))), block(64 * kPostWaves);
+  const bool all = col < 0;
+  switch (2 * kind + (all ? 1 : 0)) {
+    case 0: hipLaunchKernelGGL((k_class_out<XPG_CLASS_NONE, false>), grid, block, 0, st, a); break;
+    case 1: hipLaunchKernelGGL((k_class_out<XPG_CLASS_NONE, true>), grid, block, 0, st, a); break;
+    case 2: hipLaunchKernelGGL((k_class_out<XPG_CLASS_SOFTMAX, false>), grid, block, 0, st, a); break;
+    case 3: hipLaunchKernelGGL((k_class_out<XPG_CLASS_SOFTMAX, true>), grid, block, 0, st, a); break;
+    case 4: hipLaunchKernelGGL((k_class_out<XPG_CLASS_LOG_SOFTMAX, false>), grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL((k_class_out<XPG_CLASS_LOG_SOFTMAX, true>), grid, block, 0, st, a); break;
+  }
+  XPG_LAUNCHED();
+  return XPG_OK;
+}
+
 // ------------------------------------------------------------------------------------ helpers
 size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
+
+// the host checks of a plan's class readout (xpgnn.h, xpg_class_out): before any launch.  *n_real:
+// the class count C (the head's last n_real, or the last conv's f_out of a headless plan)
+int class_plan_check(const xpg_forward_plan* p, const xpg_post_desc* post, const xpg_class_out* cls,
+                     int* n_real = nullptr) {
+  if (!cls) return XPG_OK;
+  XPG_REQ(cls->kind >= XPG_CLASS_NONE && cls->kind <= XPG_CLASS_LOG_SOFTMAX,
+          "masked_forward: class kind outside enum xpg_class_kind");
+  XPG_REQ(!p->edge_masks, "masked_forward: a class readout does not take edge-mask plans (edge_masks)");
+  XPG_REQ(!p->edge_dot, "masked_forward: a class readout does not take a link decoder (edge_dot)");
+  for (int l = 0; l < p->n_layers; ++l)
+    XPG_REQ(p->layers[l].tgt_type == nullptr && p->layers[l].n_types <= 1,
+            "masked_forward: a class readout does not take multi-node-type plans (tgt_type)");
+  XPG_REQ(p->n_head >= 0 && (p->n_head == 0 || p->head != nullptr), "masked_forward: head layers missing");
+  const xpg_layer_desc& last = p->layers[p->n_layers - 1];
+  const int C = p->n_head > 0 ? p->head[p->n_head - 1].n_real : last.f_out;
+  const int ld = p->n_head > 0 ? p->head[p->n_head - 1].n_pad : last.f_out_pad;
+  XPG_REQ(ld >= 4 && ld <= 256 && ld % 4 == 0 && C >= 1 && C <= ld, "masked_forward: class readout widths");
+  XPG_REQ(cls->col >= -1 && cls->col < C, "masked_forward: class col outside [-1, C)");
+  if (cls->kind != XPG_CLASS_NONE) {
+    const int act = p->n_head > 0 ? p->head[p->n_head - 1].act
+                                  : (last.act != XPG_ACT_NONE ? last.act : (post ? post[p->n_layers - 1].act : 0));
+    XPG_REQ(act == XPG_ACT_NONE,
+            "masked_forward: softmax / log_softmax over a last layer with an element-wise activation");
+  }
+  if (n_real) *n_real = C;
+  return XPG_OK;
+}
 
 // plans with a post-op on any layer run on the multi-kernel path only
 bool plan_has_post(const xpg_forward_plan* p, const xpg_post_desc* post) {
@@ -8780,6 +8920,12 @@ int xpg_forward_workspace_w(const xpg_forward_plan* plan, const xpg_post_desc* p
 // Edge features add nothing to that layout (the multi-kernel path's).
 int xpg_forward_workspace_e(const xpg_forward_plan* plan, const xpg_post_desc* post, const xpg_edge_weights* wts,
                             const xpg_edge_feats* feats, int64_t rows, size_t* bytes) {
+  return xpg_forward_workspace_c(plan, post, wts, feats, nullptr, rows, bytes);
+}
+
+// Nor does a class readout: it reads the last layer's rows (the unfused tail's) and writes y.
+int xpg_forward_workspace_c(const xpg_forward_plan* plan, const xpg_post_desc* post, const xpg_edge_weights* wts,
+                            const xpg_edge_feats* feats, const xpg_class_out* cls, int64_t rows, size_t* bytes) {
   int rc = weights_plan_check(plan, wts);
   if (rc) return rc;
   rc = feats_plan_check(plan, wts, feats);
@@ -8789,8 +8935,10 @@ int xpg_forward_workspace_e(const xpg_forward_plan* plan, const xpg_post_desc* p
   if (rc) return rc;
   rc = post_plan_check(plan, post);
   if (rc) return rc;
+  rc = class_plan_check(plan, post, cls);
+  if (rc) return rc;
   WideWs W;
-  if (!plan_has_post(plan, post) && !wts && !feats && wide_wanted(plan) && wide_layout(plan, rows, &W) == 0) {
+  if (!plan_has_post(plan, post) && !wts && !feats && !cls && wide_wanted(plan) && wide_layout(plan, rows, &W) == 0) {
     *bytes = W.total;  // 32-row passes: one buffer set, or two when rows > 32
     return XPG_OK;
   }
@@ -8814,6 +8962,12 @@ int xpg_forward_describe_w(const xpg_forward_plan* p, const xpg_post_desc* post,
 
 int xpg_forward_describe_e(const xpg_forward_plan* p, const xpg_post_desc* post, const xpg_edge_weights* wts,
                            const xpg_edge_feats* feats, int64_t rows, char* buf, size_t n) {
+  return xpg_forward_describe_c(p, post, wts, feats, nullptr, rows, buf, n);
+}
+
+int xpg_forward_describe_c(const xpg_forward_plan* p, const xpg_post_desc* post, const xpg_edge_weights* wts,
+                           const xpg_edge_feats* feats, const xpg_class_out* cls, int64_t rows, char* buf,
+                           size_t n) {
   XPG_REQ(buf != nullptr && n > 0, "forward_describe: no buffer");
   buf[0] = 0;
   int rc = weights_plan_check(p, wts);
@@ -8826,10 +8980,12 @@ int xpg_forward_describe_e(const xpg_forward_plan* p, const xpg_post_desc* post,
   XPG_REQ(p->n_rel >= 1 && p->n0 >= 1 && p->cols > 0, "masked_forward: bad plan sizes");
   rc = post_plan_check(p, post);
   if (rc) return rc;
+  rc = class_plan_check(p, post, cls);
+  if (rc) return rc;
   const bool has_post = plan_has_post(p, post);
   WideWs W;
   FwdPath path;
-  rc = forward_route(p, rows, &W, &path, nullptr, has_post || wts != nullptr || feats != nullptr);
+  rc = forward_route(p, rows, &W, &path, nullptr, has_post || wts != nullptr || feats != nullptr || cls != nullptr);
   if (rc) return rc;
   if (path == kPathNone) return fail(XPG_EINVAL, kStrictMsg);
   std::string s = kPathName[path];
@@ -8844,6 +9000,7 @@ int xpg_forward_describe_e(const xpg_forward_plan* p, const xpg_post_desc* post,
   if (has_post)  // each post layer's kernel, by layer number (1-based, as l1 / l2 above)
     for (int l = 0; l < p->n_layers; ++l)
       if (post_any(post[l])) s += " post" + std::to_string(l + 1) + "=" + post_kernel_name(post[l]);
+  if (cls) s += std::string(" class=") + class_kernel_name(cls->kind, cls->col < 0);  // the tail's kernel
   if (s.size() + 1 > n) return fail(XPG_ENOSPC, "forward_describe: buffer too small");
   std::memcpy(buf, s.c_str(), s.size() + 1);
   return XPG_OK;
@@ -8885,6 +9042,11 @@ int xpg_pool_describe(int64_t rows, int64_t n, int64_t ld, int32_t kind, char* b
   return XPG_OK;
 }
 
+int xpg_class_out_rows(const float* in, int64_t M, int64_t ld, int64_t n_real, int32_t kind, int32_t col, float* out,
+                       xpg_stream_t stream) {
+  return launch_class_out(in, M, ld, n_real, kind, col, out, S(stream));
+}
+
 int xpg_post_rows(float* h, int64_t M, int64_t ld, int64_t f_out, const xpg_post_desc* post, const float* hprev,
                   int64_t ld_prev, int64_t n_tgt, int64_t n_prev, const int32_t* tgt_prev, xpg_stream_t stream) {
   XPG_REQ(post != nullptr, "post_rows: no record");
@@ -8924,6 +9086,12 @@ int xpg_masked_forward_w(const xpg_forward_plan* p, const xpg_post_desc* post, c
 int xpg_masked_forward_e(const xpg_forward_plan* p, const xpg_post_desc* post, const xpg_edge_weights* wts,
                          const xpg_edge_feats* feats, const uint32_t* bits, int64_t rows, float* y, void* workspace,
                          size_t workspace_bytes, xpg_stream_t stream) {
+  return xpg_masked_forward_c(p, post, wts, feats, nullptr, bits, rows, y, workspace, workspace_bytes, stream);
+}
+
+int xpg_masked_forward_c(const xpg_forward_plan* p, const xpg_post_desc* post, const xpg_edge_weights* wts,
+                         const xpg_edge_feats* feats, const xpg_class_out* cls, const uint32_t* bits, int64_t rows,
+                         float* y, void* workspace, size_t workspace_bytes, xpg_stream_t stream) {
   int rc = weights_plan_check(p, wts);
   if (rc) return rc;
   rc = feats_plan_check(p, wts, feats);
@@ -8933,6 +9101,9 @@ int xpg_masked_forward_e(const xpg_forward_plan* p, const xpg_post_desc* post, c
   if (rc) return rc;
   XPG_REQ(p->n_rel >= 1 && p->n0 >= 1 && p->cols > 0, "masked_forward: bad plan sizes");
   rc = post_plan_check(p, post);
+  if (rc) return rc;
+  int n_class = 0;
+  rc = class_plan_check(p, post, cls, &n_class);
   if (rc) return rc;
   const bool has_post = plan_has_post(p, post);
   XPG_REQ(!p->edge_masks || !(plan_has_kind(p, XPG_TERM_SUM) || plan_has_kind(p, XPG_TERM_MAX)),
@@ -8946,7 +9117,8 @@ int xpg_masked_forward_e(const xpg_forward_plan* p, const xpg_post_desc* post, c
   // hold (a wide plan returns before `go` is read; its workspace is checked below)
   const bool ready = workspace_bytes >= L.total && rows != 0;
   const FwdLaunch go{bits, y, st, workspace ? reinterpret_cast<int*>(static_cast<char*>(workspace) + L.ctl) : nullptr};
-  rc = forward_route(p, rows, &W, &path, ready ? &go : nullptr, has_post || wts != nullptr || feats != nullptr);
+  rc = forward_route(p, rows, &W, &path, ready ? &go : nullptr,
+                     has_post || wts != nullptr || feats != nullptr || cls != nullptr);
   if (rc) return rc;
   if (path == kPathWide) {
     XPG_REQ(workspace_bytes >= W.total, "masked_forward: workspace too small");
@@ -8974,7 +9146,8 @@ int xpg_masked_forward_e(const xpg_forward_plan* p, const xpg_post_desc* post, c
   // Nor may a last conv layer with a post-op take the column pick or the first head layer into its
   // k_dense epilogue: the post-op runs between the two.
   const bool last_post = has_post && post_any(post[p->n_layers - 1]);
-  if (!p->edge_dot && p->n_head >= 1 &&
+  // Nor does a class readout fuse: the HEAD epilogue keeps one column, softmax needs them all.
+  if (!cls && !p->edge_dot && p->n_head >= 1 &&
       (p->n_head >= 2 || (p->n_layers >= 2 && !pool && !last_att2 && !last_post))) {
     const xpg_head_desc& hl = p->head[p->n_head - 1];
     const int64_t prev_pad = p->n_head >= 2 ? p->head[p->n_head - 2].n_pad : p->layers[p->n_layers - 1].f_out_pad;
@@ -9219,6 +9392,8 @@ int xpg_masked_forward_e(const xpg_forward_plan* p, const xpg_post_desc* post, c
     else
       hipLaunchKernelGGL(k_edge_dot, dim3(static_cast<unsigned>(cdiv(rows, 256))), dim3(256), 0, st, cur, rows,
                          last.n_tgt, cur_ld, n_real, p->dot_a, p->dot_b, p->dot_act, y);
+  } else if (cls) {  // y [M] (one class) or [M][C] (all), plan->out_col unread
+    return launch_class_out(cur, M, cur_ld, n_class, cls->kind, cls->col, y, st);
   } else {
     hipLaunchKernelGGL(k_take_col, dim3(static_cast<unsigned>(cdiv(M, 256))), dim3(256), 0, st, cur, M, cur_ld,
                        p->out_col, y);

@@ -552,6 +552,28 @@ def pool_rows(h: torch.Tensor, kind: str, out: torch.Tensor = None,
     return out
 
 
+# ----------------------------------------------------------------------------- class readout
+def class_out_rows(z: torch.Tensor, n_real: int, kind=None, col: int = -1,
+                   out: torch.Tensor = None) -> torch.Tensor:
+    """The class readout of z [M, ld] fp32 (ld % 4 == 0, at most 256; the first n_real columns are
+    the classes, the rest padding that is never read as a value) on its own (xpg_class_out_rows;
+    the tail of a ForwardPlan with a class readout): `kind` None / "softmax" / "log_softmax" over
+    the n_real columns, then class `col` -> [M], or every class (col = -1) -> [M, n_real].
+    Deterministic: a row's result depends on its values and (n_real, ld) alone."""
+    _lib.require_device(z, "z")
+    if z.dtype != torch.float32 or z.dim() != 2 or not z.is_contiguous():
+        raise ValueError("z must be a contiguous float32 [M, ld] tensor")
+    M, ld = z.shape
+    shape = (M,) if col >= 0 else (M, int(n_real))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=z.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32 {list(shape)} tensor")
+    call("xpg_class_out_rows", ptr(z), M, ld, int(n_real), _lib.CLASS_KIND[kind], int(col), ptr(out),
+         _lib.stream_of(z.device))
+    return out
+
+
 # ----------------------------------------------------------------------------- post-op
 def _post_record(ld, norm, eps, act, residual, vecs, device, keep):
     pd = _lib.PostDesc(norm=_lib.NORM[norm], eps=float(eps), act=ACT[act], residual=int(bool(residual)))
@@ -953,7 +975,7 @@ class ForwardPlan:
     """Receptive-field plan of one (subgraph, model program, query set)."""
 
     def __init__(self, program, sub_feat, rel_edges, queries, device=None, node_type=None,
-                 edge_cols=None, link=None, edge_weight=None, edge_attr=None):
+                 edge_cols=None, link=None, edge_weight=None, edge_attr=None, out_col=None, classes=None):
         """`node_type` ([S] node type of every subgraph node) is required by multi-node-type
         programs: per layer, every target's type gates the relation terms (xpgnn.h).
 
@@ -981,7 +1003,15 @@ class ForwardPlan:
         edge_attr=True.  The plan carries each layer's mapped edge rows gathered into its CSR
         orders (edge_feature_arrays; xpgnn.h, xpg_edge_feats) and runs on k_agg_e; every layer takes
         the aggregate-then-transform form, so the input may be at most 256 columns wide after
-        padding to 32.  Node masks, one relation, one node type; not together with edge_weight."""
+        padding to 32.  Node masks, one relation, one node type; not together with edge_weight.
+
+        `out_col` (class c of a model with C output columns; None: the program's own out_col, 0)
+        and `classes` (None, or "all"): which output columns forward returns.  On a program without `out_norm`, `out_col`
+        alone fills the descriptor's out_col and the plan keeps every path.  A program that ends in
+        softmax / log_softmax (`program.out_norm`), or classes="all", carries a class readout
+        (xpgnn.h, xpg_class_out; k_class_out on the multi-kernel path): forward returns
+        [rows, n_targets] for one class, [rows, n_targets * C] in (target, class) order for all.
+        Node masks, single-node-type programs, no link decoder."""
         device = torch.device(device) if device is not None else sub_feat.device
         _lib.require_device(torch.empty(0, device=device), "plan device")
         if len(program.convs) == 0:
@@ -1362,11 +1392,36 @@ class ForwardPlan:
             prev_pad = n_pad
 
         self.n_out = fr[L].size
+        # the output column(s): descriptor out_col, or a class readout beside the plan
+        self.n_classes = program.n_classes
+        self.out_norm = getattr(program, "out_norm", None)
+        if classes not in (None, "all"):
+            raise ValueError(f"classes must be None or 'all', got {classes!r}")
+        if out_col is None:
+            out_col = program.out_col
+        if isinstance(out_col, bool) or not isinstance(out_col, (int, np.integer)):
+            raise TypeError("out_col must be an int")
+        if not 0 <= int(out_col) < self.n_classes:
+            raise ValueError(f"out_col {out_col} outside [0, {self.n_classes})")
+        self.out_col, self.classes = int(out_col), classes
+        self._cls = None
+        if self.out_norm is not None or classes == "all":
+            if self.out_norm not in _lib.CLASS_KIND:
+                raise ValueError(f"unknown out_norm {self.out_norm!r}")
+            if self.edge_masks or link is not None:
+                raise ValueError("a class readout (softmax / all classes) on edge-mask plans is not supported")
+            if program.n_types > 1:
+                raise ValueError("a class readout (softmax / all classes) on multi-node-type programs "
+                                 "is not supported")
+            self._cls = _lib.ClassOut(kind=_lib.CLASS_KIND[self.out_norm],
+                                      col=-1 if classes == "all" else self.out_col)
+        elif self.out_col != 0 and link is not None:
+            raise ValueError("out_col on a link decoder plan is not supported")
         self.desc = ForwardPlanDesc(
             cols=self.cols, n_rel=self.n_rel, n0=n0,
             n_deg_edges=int(arr["deg_src"].size), n_layers=L,
             layers=self._layers, n_head=len(program.head), head=self._head,
-            out_col=program.out_col)
+            out_col=program.out_col if self._cls is not None else self.out_col)
         self._i32(self.desc, "f0_node", fr[0])
         self._i32(self.desc, "deg_ptr", arr["deg_ptr"])
         self._i32(self.desc, "deg_src", arr["deg_src"] if arr["deg_src"].size else np.zeros(1))
@@ -1394,6 +1449,9 @@ class ForwardPlan:
             self.n_out = 1
         if self.pool is not None:
             self.n_out = 1  # forward returns [rows, 1], as link plans do
+        self.n_targets = self.n_out
+        if classes == "all":
+            self.n_out = self.n_targets * self.n_classes  # (target, class) order
         self._upload_i32()
         # edge weights (xpgnn.h, xpg_edge_weights): every array in one upload
         self._weights = None
@@ -1488,6 +1546,11 @@ class ForwardPlan:
     def _entry(self, name):
         """The entry point and its leading arguments: `name`(plan, ...), or with post-ops
         `name`_post(plan, post records, ...)."""
+        if self._cls is not None:  # `name`_c(plan, post records, weights, features (each or NULL), class readout, ...)
+            return name + "_c", (ctypes.byref(self.desc), self._post,
+                                 ctypes.byref(self._weights) if self._weights is not None else None,
+                                 ctypes.byref(self._feats) if self._feats is not None else None,
+                                 ctypes.byref(self._cls))
         if self._feats is not None:  # `name`_e(plan, post records or NULL, NULL weights, features, ...)
             return name + "_e", (ctypes.byref(self.desc), self._post, None, ctypes.byref(self._feats))
         if self._weights is not None:  # `name`_w(plan, post records or NULL, weights, ...)
@@ -1507,7 +1570,8 @@ class ForwardPlan:
         "fused", "unfused", or "wide l1=<kernel> l2=<kernel>" with the kernels' template
         arguments; a plan with post-ops: "unfused post<l>=k_post<NORM,RES> ..." (each post layer's
         kernel); a weighted plan: "unfused weights=k_degree_w+k_agg_w" before those tokens; an
-        edge-featured plan: "unfused efeat=k_agg_e" before them.  A host query of the library's own dispatch (nothing is launched); raises
+        edge-featured plan: "unfused efeat=k_agg_e" before them; a plan with a class readout ends in
+        " class=k_class_out<kind,one|all>".  A host query of the library's own dispatch (nothing is launched); raises
         where forward() would refuse the plan (XPG_FORWARD_STRICT=1)."""
         buf = ctypes.create_string_buffer(1024)
         name, lead = self._entry("xpg_forward_describe")

@@ -169,6 +169,27 @@ class Explainer:
         return bool(self.params.get("attention_engine", False))
 
     @property
+    def target_class(self):
+        """params["target_class"] (default 0): the output column c of a model with C outputs whose
+        value is explained, after the model's own softmax / log_softmax when it ends in one.  An int
+        >= 0; a class outside [0, C) raises ValueError once C is known (the compiled program's
+        width, or the module's output on the generic path).  Non-zero classes: node_prediction and
+        graph_prediction over node masks on graphs of one node type."""
+        tc = self.params.get("target_class", 0)
+        if isinstance(tc, bool) or not isinstance(tc, (int, np.integer)) or tc < 0:
+            raise ValueError(f"params['target_class'] must be an int >= 0, got {tc!r}")
+        return int(tc)
+
+    def _check_class_support(self, c, what):
+        """Class columns other than 0 (and run_classes): not on edge problems / edge masks, nor on
+        graphs of more than one node type."""
+        if "edge" in self.problem or "link" in self.problem or self.edge_masks:
+            raise NotImplementedError(f"{what} on edge problems / edge masks is not supported")
+        if c["h_ntypes"] is not None and c["sub_nt"] is not None and \
+                len(torch.unique(c["sub_nt"])) >= 2:
+            raise NotImplementedError(f"{what} on a graph of more than one node type is not supported")
+
+    @property
     def edge_masks(self):
         """Non-compat edge problems (params["edge_masks"] = True): mask columns
         are the computational graph's edges (Data.perturb_edge, data.py:500-554) and the arch is
@@ -278,7 +299,7 @@ class Explainer:
                 bool(getattr(plan, "multi_type", False)),
                 tuple(c["h_ntypes"] or ()), tuple(c["h_etypes"] or ()),
                 tuple(getattr(plan, "lowering", ())), self.edge_weight is not None,
-                self.edge_attr is not None)
+                self.edge_attr is not None, self.target_class)
 
     def _query_key(self, element, device):
         """The cache slot of a query: element, problem, device and modes.  Whether the slot's
@@ -287,7 +308,8 @@ class Explainer:
         stream as the reference's)."""
         return (str(element), type(element).__name__, self.problem, self.edge_masks, str(device),
                 _freeze(self.element_type), str(self.params.get("verify_arch", True)),
-                self.attention_engine, self.edge_weight is not None, self.edge_attr is not None)
+                self.attention_engine, self.edge_weight is not None, self.edge_attr is not None,
+                self.target_class)
 
     def _query_sources(self, params, bufs):
         """Identity snapshot of what prepare() and the query's ForwardPlan read: the graph and
@@ -471,6 +493,7 @@ class Explainer:
             raise _lib.NativeLibraryError("Explainer.run needs an MI355X (HIP) device; "
                                           "there is no CPU fallback")
         _lib.load()
+        tc = self.target_class
         device = torch.device("cuda", torch.cuda.current_device())
         clock = PhaseClock(torch.cuda.current_stream(device))
         clock.mark("setup")
@@ -495,6 +518,8 @@ class Explainer:
                 del self._queries[qkey]  # stale: the inputs changed since it was prepared
         hit = cached is not None
         c = cached[0] if cached else self.prepare(element, device)
+        if tc != 0:
+            self._check_class_support(c, f"params['target_class'] = {tc}")
         sub_feat, sub_ei, sub_ind, S = c["sub_feat"], c["sub_ei"], c["sub_ind"], c["S"]
         geo = (c["sub_nt"], c["sub_et"], c["h_ntypes"], c["h_etypes"], c["padded_dims"])
 
@@ -582,7 +607,8 @@ class Explainer:
                                                        **typed)
         else:
             plan = pipeline.build_plan(self.arch, sub_feat, sub_ei, [sub_ind], *geo,
-                                       module_state=mstate, attention=self.attention_engine, **wkw)
+                                       module_state=mstate, attention=self.attention_engine,
+                                       out_col=tc, **wkw)
             verify = lambda: pipeline.verify_plan(plan, self.arch, sub_feat, sub_ei, sub_ind, *geo, **wkw)
         clock.mark("verify")
         arch_check = "off"
@@ -657,7 +683,8 @@ class Explainer:
                 ys = [pipeline.generic_outputs(
                     self.arch, sub_feat, sub_ei,
                     engine.unpack_masks(bits[i], S) if masks[i] is None else masks[i],
-                    sub_ind, self.problem, *geo, batch=batch, q4=q4, **wkw) for i in range(t0, t1)]
+                    sub_ind, self.problem, *geo, batch=batch, q4=q4, out_col=tc, **wkw)
+                    for i in range(t0, t1)]
                 return torch.stack(ys) if ys else torch.empty((0, R), device=device)
             y = sharding.gather_map(times, generic, g)
 
@@ -710,7 +737,7 @@ class Explainer:
             self._trim_cache(qkey)
         self.last_run = {"engine": plan is not None, "repeats": diag, "S": S,
                          "sub_ind": sub_ind, "plan": plan, "weights": w.unbind(0),
-                         "phases": clock, "arch_check": arch_check,
+                         "phases": clock, "arch_check": arch_check, "target_class": tc,
                          "query_cache": "off" if qkey is None else "hit" if hit else "miss",
                          # graph-level readout of a pooled arch ("mean" | "sum" | "max"), else None
                          "pool": plan.pool if plan is not None else
@@ -836,6 +863,154 @@ class Explainer:
         self.last_run = {"engine": True, "queries": inds, "S": S, "rows": R, "batch": batch,
                          "bits": bits, "y": y, "kernel": kern, "w0": w0_all.reshape(Q, times, S),
                          "weights": fitted, "plan": plan}
+        return out
+
+    def run_classes(self, element, classes=None, times=1):
+        """Several classes of ONE query over one mask set per repeat: the explanation of every
+        requested output column of a multi-class model (after its own softmax / log_softmax when it
+        ends in one) for the price of one.
+
+        The masks, the masked message passing and KernelSHAP do not depend on the class, so each
+        repeat's masks are drawn once, one forward returns every class column per row (a
+        ForwardPlan with classes="all"; a subset is a column slice), KernelSHAP runs once and each
+        class gets its own surrogate fits (all len(classes) x times of them in one launch while
+        the replicated mask rows stay under params["run_queries_batch_bytes"], default 2 GiB; else
+        one launch per class).  `classes`: a list of distinct ints in [0, C), None = all C (C: the
+        compiled program's output width, else the module's own).  RNG order per repeat: masks,
+        then one LinearRegression init per class, then the DataLoader seed draw, so
+        `run_classes(e, [c]) == [run(e)]` with params["target_class"] = c (to the fit's 1e-4 bar
+        when the batched launch splits each fit over fewer workgroups).  node_prediction and
+        graph_prediction over node masks, one node type; pooled (graph-level) archs included.  An
+        arch the engine cannot compile runs through the module itself (all columns from the one
+        arch call per batch), with the usual warning.  Multi-GPU: forward / KernelSHAP rows and fit
+        units are sharded over ranks as in run_queries.  Returns [(config_val_df, pathway_df)] in
+        class order."""
+        if not torch.cuda.is_available():
+            raise _lib.NativeLibraryError("Explainer.run_classes needs an MI355X (HIP) device; "
+                                          "there is no CPU fallback")
+        _lib.load()
+        device = torch.device("cuda", torch.cuda.current_device())
+        if times == 1:
+            set_seed(self.params["seed"])
+        g = self.group
+        sharding.sync_rng(g)
+        _, _, mstate = self._place_arch(device)
+        c = self.prepare(element, device)
+        self._check_class_support(c, "run_classes")
+        sub_feat, sub_ei, sub_ind, S = c["sub_feat"], c["sub_ei"], c["sub_ind"], c["S"]
+        geo = (c["sub_nt"], c["sub_et"], c["h_ntypes"], c["h_etypes"], c["padded_dims"])
+        wkw = self._edge_kw(c)
+        plan = pipeline.build_plan(self.arch, sub_feat, sub_ei, [sub_ind], *geo, module_state=mstate,
+                                   attention=self.attention_engine, classes="all", **wkw)
+        arch_check = "off"
+        if plan is not None and self.params.get("verify_arch", True):
+            ok, err = pipeline.verify_plan(plan, self.arch, sub_feat, sub_ei, sub_ind, *geo, **wkw)
+            arch_check = "verified" if ok else "failed"
+            if not ok:
+                warnings.warn(f"compiled arch disagrees with its torch forward (max err "
+                              f"{err:.3g}); using the generic torch path")
+                plan = None
+        if plan is not None:
+            C = plan.n_classes
+        else:  # the module's own output width, from one unperturbed copy (no RNG consumed)
+            C = int(pipeline.generic_outputs(
+                self.arch, sub_feat, sub_ei, torch.ones((1, S), dtype=torch.bool, device=device),
+                sub_ind, self.problem, *geo, classes="all", **wkw).shape[1])
+        if classes is None:
+            classes = list(range(C))
+        classes = list(classes)
+        for k in classes:
+            if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= k < C:
+                raise ValueError(f"run_classes: class {k!r} outside [0, {C}): the model has {C} "
+                                 "output column(s)")
+        classes = [int(k) for k in classes]
+        Q = len(classes)
+        if Q == 0 or len(set(classes)) != Q:
+            raise ValueError("run_classes: classes must be a non-empty list of distinct ints")
+        sampler = self.params.get("mask_sampler", "compat")
+        _, epochs = Mask.assertions_mask_generator(self.params)
+        if sampler == "device" and c["sub_pw_inds"] is not None:
+            cmask = Mask(sub_feat, sub_ei, c["sub_pw_inds"], self.params, self.problem)
+            cplan = cmask.community_plan()
+            ctabs = engine.community_tables(cplan, c["sub_pw_inds"], S, device)
+        bits_list, w0 = [], [[] for _ in range(Q)]
+        for _ in range(times):
+            if sampler == "device":
+                R = int(self.params["interpret_samples"] * epochs)
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+                bits_list.append(engine.sample_shapley(seed, R, S, device)
+                                 if c["sub_pw_inds"] is None else
+                                 engine.sample_communities(seed, cplan, c["sub_pw_inds"], S,
+                                                           device, tables=ctabs)[0])
+            else:  # compat: the reference's CPU draws, bit-identical, packed on the device
+                bits_list.append(Mask(sub_feat, sub_ei, c["sub_pw_inds"], self.params,
+                                      self.problem).generate_bits(device)[0])
+            for q in range(Q):
+                w0[q].append(LinearRegression.initial_weights(S))
+            dataloader_seed_draw()
+        R = bits_list[0].shape[0]
+        batch = R // epochs
+        bits = torch.stack(bits_list)                       # [times, R, W]
+        w0_all = torch.stack([w for wq in w0 for w in wq])  # [Q * times, S], class-major
+        sharding.assert_replicated(bits, "mask rows", g)
+        sharding.assert_replicated(w0_all, "initial surrogate weights", g)
+        flat = bits.reshape(times * R, -1)
+        if plan is not None:  # one forward, every class column; the requested ones are a slice
+            y = sharding.gather_map(times * R, lambda s, e: plan.forward(flat[s:e]), g)
+            y = y.reshape(times, R, C)
+        else:
+            def generic(t0, t1):
+                ys = [pipeline.generic_outputs(self.arch, sub_feat, sub_ei, engine.unpack_masks(bits[i], S),
+                                               sub_ind, self.problem, *geo, batch=batch, classes="all",
+                                               **wkw) for i in range(t0, t1)]
+                return torch.stack(ys) if ys else torch.empty((0, R, C), device=device)
+            y = sharding.gather_map(times, generic, g)
+        y = y[:, :, classes].contiguous()                   # [times, R, Q]
+
+        def kernel_rows(s, e):
+            if e == s:
+                return torch.empty(0, dtype=torch.float64, device=device)
+            return engine.shap_kernel(flat[s:e], S)
+        kern = sharding.gather_map(times * R, kernel_rows, g).reshape(times, R)
+        limit = int(self.params.get("run_queries_batch_bytes", 2 << 30))
+
+        def fit(u0, u1):
+            # units u = q * times + i (class position q, repeat i), a contiguous shard of them
+            if u1 == u0:
+                return torch.empty((0, S), device=device)
+            us = torch.arange(u0, u1, device=device)
+            q_of, i_of = us // times, us % times
+            if (u1 - u0) * bits[0].numel() * 4 <= limit:
+                ws, _, _, _, _ = engine.wlm_fit(
+                    bits[i_of], S, batch, y[i_of, :, q_of], kern[i_of], w0_all[u0:u1],
+                    self.params)
+                return ws
+            out = []  # one launch per class (its repeats batched)
+            for q in range(int(q_of[0]), int(q_of[-1]) + 1):
+                sel = (q_of == q).nonzero().reshape(-1)
+                ii = i_of[sel]
+                out.append(engine.wlm_fit(bits[ii], S, batch, y[ii, :, q], kern[ii],
+                                          w0_all[(u0 + sel).cpu()], self.params)[0])
+            return torch.cat(out)
+        fitted = sharding.gather_map(Q * times, fit, g).reshape(Q, times, S)
+        labels = frames.name_labels(c["sub_names"]) if c["pos"] is not None else None
+        out = []
+        for q in range(Q):
+            mean, std = self.weight_stacking(fitted[q])
+            ms = torch.stack([mean.detach(), std.detach()]).cpu().numpy()
+            df = frames.sorted_frame(c["sub_names"], {"config_value_mean": ms[0],
+                                                      "config_value_std": ms[1]},
+                                     "config_value_mean", labels=labels)
+            pdf = None
+            if c["has_pathways"]:
+                pdf = Pathways(c["sub_pw"], c["sub_pw_names"]).aggregate(mean, c["sub_pw_inds"])
+            out.append((df, pdf))
+        self.last_run = {"engine": plan is not None, "classes": classes, "n_classes": C, "S": S,
+                         "sub_ind": sub_ind, "rows": R, "batch": batch, "bits": bits, "y": y,
+                         "kernel": kern, "w0": w0_all.reshape(Q, times, S), "weights": fitted,
+                         "plan": plan, "arch_check": arch_check,
+                         "pool": plan.pool if plan is not None else
+                         (POOL_KIND.get(getattr(self.arch, "pool", None)) if self.pooled else None)}
         return out
 
 

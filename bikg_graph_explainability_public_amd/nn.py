@@ -540,6 +540,18 @@ def _edge_kwargs(edge_weight, edge_attr):
     return {} if edge_attr is None else {"edge_attr": edge_attr}
 
 
+def _final_act(final_act):
+    """The unit after a stack's last Linear: "sigmoid", a multi-class classifier's "softmax" /
+    "log_softmax" over the class (last) dimension, anything else the identity."""
+    if final_act == "sigmoid":
+        return nn.Sigmoid()
+    if final_act == "softmax":
+        return nn.Softmax(dim=-1)
+    if final_act == "log_softmax":
+        return nn.LogSoftmax(dim=-1)
+    return nn.Identity()
+
+
 class ConvStack(nn.Module):
     """Model family of the reference tests/notebooks (tests/test_utils.py:10-83,
     examples/toy_example-caseA.ipynb cell 9): `conv` = ModuleList[Conv, ReLU]*, `fc` =
@@ -605,8 +617,7 @@ class ConvStack(nn.Module):
         for i in range(len(fc_dims) - 1):
             fcs.append(Linear(fc_dims[i], fc_dims[i + 1]))
             last = i == len(fc_dims) - 2
-            fcs.append((nn.Sigmoid() if final_act == "sigmoid" else nn.Identity()) if last
-                       else nn.ReLU())
+            fcs.append(_final_act(final_act) if last else nn.ReLU())
         self.fc = nn.ModuleList(fcs)
 
     def forward(self, x, edge_index, edge_weight=None, edge_attr=None):
@@ -698,8 +709,7 @@ class BlockStack(nn.Module):
         for i in range(len(fc_dims) - 1):
             fcs.append(Linear(fc_dims[i], fc_dims[i + 1]))
             last = i == len(fc_dims) - 2
-            fcs.append((nn.Sigmoid() if final_act == "sigmoid" else nn.Identity()) if last
-                       else nn.ReLU())
+            fcs.append(_final_act(final_act) if last else nn.ReLU())
         self.fc = nn.ModuleList(fcs)
 
     def forward(self, x, edge_index, edge_weight=None, edge_attr=None):
@@ -735,8 +745,7 @@ class RGCNStack(nn.Module):
         for i in range(len(fc_dims) - 1):
             fcs.append(Linear(fc_dims[i], fc_dims[i + 1]))
             last = i == len(fc_dims) - 2
-            fcs.append((nn.Sigmoid() if final_act == "sigmoid" else nn.Identity()) if last
-                       else nn.ReLU())
+            fcs.append(_final_act(final_act) if last else nn.ReLU())
         self.fc = nn.ModuleList(fcs)
 
     def forward(self, x, edge_index, node_types, edge_types):
@@ -935,8 +944,7 @@ class PooledModel(nn.Module):
         for i in range(len(fc_dims) - 1):
             fcs.append(Linear(fc_dims[i], fc_dims[i + 1]))
             last = i == len(fc_dims) - 2
-            fcs.append((nn.Sigmoid() if final_act == "sigmoid" else nn.Identity()) if last
-                       else nn.ReLU())
+            fcs.append(_final_act(final_act) if last else nn.ReLU())
         self.fc = nn.ModuleList(fcs)
 
     def forward(self, x, edge_index, batch=None, edge_weight=None, edge_attr=None):

@@ -86,7 +86,7 @@ def compiled_program(arch, edge_type_names=None, node_type_names=None, state=Non
     key = (id(arch), state,
            tuple(tuple(e) for e in edge_type_names) if edge_type_names is not None else None,
            tuple(node_type_names) if node_type_names is not None else None, bool(attention),
-           bool(edge_weight), bool(edge_attr))
+           bool(edge_weight), bool(edge_attr), module_out_norm(arch))
     hit = _PROGRAMS.get(key)
     if hit is not None and hit[0]() is arch:
         _PROGRAMS.move_to_end(key)
@@ -99,9 +99,41 @@ def compiled_program(arch, edge_type_names=None, node_type_names=None, state=Non
     return prog
 
 
+def module_out_norm(arch):
+    """The Softmax / LogSoftmax units of a module with their dims, in registration order: the part
+    of compiled_program's key that sees such a (parameter-free) unit added, removed or replaced."""
+    return tuple((type(m).__name__, getattr(m, "dim", None)) for m in arch.modules()
+                 if type(m).__name__ in ("Softmax", "LogSoftmax"))
+
+
+def check_class_request(out_col, classes):
+    """out_col: None (the legacy single-output extraction) or an int >= 0; classes: None or "all"."""
+    if classes not in (None, "all"):
+        raise ValueError(f"classes must be None or 'all', got {classes!r}")
+    if out_col is not None and (isinstance(out_col, bool) or not isinstance(out_col, int) or out_col < 0):
+        raise ValueError(f"out_col must be an int >= 0, got {out_col!r}")
+
+
+def pick_classes(out, rows, out_col, classes):
+    """The requested class columns of a module output for `rows` output rows: out [rows, C] (or
+    [rows], C = 1) -> [rows] for class out_col, [rows, C] for classes="all".  ValueError when the
+    class is outside [0, C): C is the module's own output width."""
+    if out.dim() == 1:
+        out = out.reshape(-1, 1)
+    if out.dim() != 2 or out.shape[0] != rows:
+        raise RuntimeError(f"model output {tuple(out.shape)} has no [{rows}, classes] form")
+    if classes == "all":
+        return out.float()
+    c = 0 if out_col is None else out_col
+    if c >= out.shape[1]:
+        raise ValueError(f"target class {c} outside [0, {out.shape[1]}): the model has "
+                         f"{out.shape[1]} output column(s)")
+    return out[:, c].float()
+
+
 def build_plan(arch, feat, edge_index, queries, node_type=None, edge_type=None,
                node_type_names=None, edge_type_names=None, padded_dims=None, module_state=None,
-               attention=False, edge_weight=None, edge_attr=None):
+               attention=False, edge_weight=None, edge_attr=None, out_col=None, classes=None):
     """ForwardPlan for `arch` on the (sub)graph, or None when the engine cannot run it.
     `attention=True` (opt-in, Explainer params["attention_engine"]) also compiles GATConv
     relations, which otherwise run on the generic torch path.
@@ -123,7 +155,12 @@ def build_plan(arch, feat, edge_index, queries, node_type=None, edge_type=None,
 
     `edge_attr` ([E, D] or [E], one row per edge of `edge_index`; homogeneous graphs): the arch is
     compiled for a graph with edge features (GINEConv only) and the plan carries the rows.
-    Attributes that are themselves invalid (wrong row count, integer, not finite) raise ValueError."""
+    Attributes that are themselves invalid (wrong row count, integer, not finite) raise ValueError.
+
+    `out_col` = c (None: column 0) / `classes` = "all": the class column(s) the plan returns
+    (engine.ForwardPlan).  A class outside the compiled program's [0, C) raises ValueError: no path
+    could return it."""
+    check_class_request(out_col, classes)
     multi = node_type_names is not None and node_type is not None and \
         len(torch.unique(node_type)) >= 2
     hetero = edge_type_names is not None and edge_type is not None
@@ -151,6 +188,9 @@ def build_plan(arch, feat, edge_index, queries, node_type=None, edge_type=None,
     if prog.link_act is not None:
         raise ValueError("a LinkModel scores edges: explain it with problem='edge_prediction' "
                          "and params['edge_masks'] = True")
+    if out_col is not None and out_col >= prog.n_classes:
+        raise ValueError(f"target class {out_col} outside [0, {prog.n_classes}): the model has "
+                         f"{prog.n_classes} output column(s)")
     x = feat
     nt = None
     if prog.pool is not None:
@@ -175,7 +215,7 @@ def build_plan(arch, feat, edge_index, queries, node_type=None, edge_type=None,
             rels = relation_edges(edge_index, edge_type if hetero else None,
                                   len(edge_type_names) if hetero else 1)
         plan = engine.ForwardPlan(prog, x, rels, queries, node_type=nt, edge_weight=edge_weight,
-                                  edge_attr=edge_attr)
+                                  edge_attr=edge_attr, out_col=out_col, classes=classes)
     except ValueError as e:
         warnings.warn(f"engine plan rejected ({e}); using the generic torch path")
         return None
@@ -360,14 +400,22 @@ def require_edge_attr_arch(arch):
 
 def generic_outputs(arch, feat, edge_index, mask, element_index, problem, node_type=None,
                     edge_type=None, node_type_names=None, edge_type_names=None,
-                    padded_dims=None, batch=None, q4=True, edge_weight=None, edge_attr=None):
+                    padded_dims=None, batch=None, q4=True, edge_weight=None, edge_attr=None,
+                    out_col=None, classes=None):
     """wlm.py:349-436 semantics per batch of mask rows with the user's module in torch.
     Returns y [R] (the regression target of each row; for multi-node-type graphs the
     reference's output[ind::S] collapse, quirk Q4, broadcast over its batch).  A list of
     element indices (single-node-type graphs) returns y [R, Q]: every query's extraction from
     the same union-graph forward.  `edge_weight` ([E], homogeneous graphs): each copy's kept
     edges carry their weights, `arch(x, edge_index[, batch], edge_weight=w)`.  `edge_attr` ([E, D],
-    homogeneous graphs): they carry their attribute rows, `arch(..., edge_attr=ea)`."""
+    homogeneous graphs): they carry their attribute rows, `arch(..., edge_attr=ea)`.
+
+    `out_col` = c: class column c of the module's own [rows, C] output instead of the legacy
+    extraction (which needs a single-output module); `classes` = "all": every column, y [R, C]
+    (a query list: [R, Q * C] in (query, class) order).  The module's output is read as it is, so a
+    model that applies a functional softmax in its forward works here.  Single-node-type graphs."""
+    check_class_request(out_col, classes)
+    by_class = out_col is not None or classes is not None
     pooled = pooled_call(arch)
     if edge_attr is not None:
         if edge_weight is not None:
@@ -388,7 +436,7 @@ def generic_outputs(arch, feat, edge_index, mask, element_index, problem, node_t
             raise ValueError("a pooled (graph-level) model has one output per graph: no query list")
         return _generic_multi(arch, feat, edge_index, mask, element_index, problem, node_type,
                               edge_type, node_type_names, edge_type_names, padded_dims, batch,
-                              edge_weight, edge_attr)
+                              edge_weight, edge_attr, out_col, classes)
     data = Data(feat, edge_index)
     mc = Model(arch)
     R, S = mask.shape
@@ -418,8 +466,13 @@ def generic_outputs(arch, feat, edge_index, mask, element_index, problem, node_t
             out = mc.infer(cf, pei, batch=gb, edge_weight=pew, edge_attr=pea)
             if out.dim() != 2 or out.shape[0] != B:
                 raise RuntimeError(f"a pooled model must return [{B}, out], got {tuple(out.shape)}")
-            ys.append(out[:, 0].reshape(-1).float())
+            ys.append(pick_classes(out, B, out_col, classes) if by_class else out[:, 0].reshape(-1).float())
             continue
+        if by_class and n_types >= 2:
+            # the reference's multi-node-type extraction reads column 0 (model.py:247)
+            if out_col or classes is not None:
+                raise NotImplementedError("class columns on a multi-node-type graph are not supported")
+            by_class = False
         if n_types < 2:
             out = mc.infer(cf, pei, cnt, pet, edge_weight=pew, edge_attr=pea)
         else:
@@ -438,6 +491,9 @@ def generic_outputs(arch, feat, edge_index, mask, element_index, problem, node_t
             out, _ = mc.hetero2homo_output(out)
         if element_index is not None and (q4 or n_types < 2):
             out = mc.extract_node_edge_output(out, element_index, S)
+        if by_class:
+            ys.append(pick_classes(out, B, out_col, classes))
+            continue
         out = out.reshape(-1).float()
         if out.numel() == B:
             ys.append(out)
@@ -451,8 +507,10 @@ def generic_outputs(arch, feat, edge_index, mask, element_index, problem, node_t
 
 def _generic_multi(arch, feat, edge_index, mask, queries, problem, node_type, edge_type,
                    node_type_names, edge_type_names, padded_dims, batch, edge_weight=None,
-                   edge_attr=None):
-    """generic_outputs for several queries of a single-node-type graph: [R, Q]."""
+                   edge_attr=None, out_col=None, classes=None):
+    """generic_outputs for several queries of a single-node-type graph: [R, Q] ([R, Q * C] with
+    classes="all", (query, class) order)."""
+    by_class = out_col is not None or classes is not None
     data = Data(feat, edge_index)
     mc = Model(arch)
     R, S = mask.shape
@@ -476,6 +534,10 @@ def _generic_multi(arch, feat, edge_index, mask, queries, problem, node_type, ed
         out = mc.infer(cf, pei, cnt, pet, edge_weight=pew, edge_attr=pea)
         if isinstance(out, dict):
             out, _ = mc.hetero2homo_output(out)
+        if by_class:
+            ys.append(torch.stack([pick_classes(mc.extract_node_edge_output(out, int(q), S), B, out_col,
+                                                classes) for q in queries], 1).reshape(B, -1))
+            continue
         ys.append(torch.stack([mc.extract_node_edge_output(out, int(q), S).reshape(-1).float()
                                for q in queries], 1).reshape(B, len(queries)))
     return torch.cat(ys)
@@ -486,25 +548,30 @@ def verify_plan(plan, arch, feat, edge_index, query, node_type=None, edge_type=N
                 edge_weight=None, edge_attr=None):
     """Check the compiled program against the user's module on a few random masks (guards the
     registration-order lowering in program.compile_arch).  `query` may be the list of a
-    multi-query plan's queries: every output column is then checked."""
+    multi-query plan's queries: every output column is then checked.  The plan's class request
+    (its out_col, or classes="all") is the one checked: every requested class."""
     g = torch.Generator(device="cpu").manual_seed(1234)
     S = feat.shape[0]
     mask = (torch.rand((rows, S), generator=g) < 0.5).to(feat.device)
     mask[0] = True
     multi = getattr(plan, "multi_type", False)
+    # the class columns of the module's own output; a multi-node-type plan (class 0 only) keeps the
+    # reference's extraction
+    ckw = {} if multi else {"out_col": getattr(plan, "out_col", 0), "classes": getattr(plan, "classes", None)}
     if isinstance(query, (list, tuple)):
         assert not multi, "multi-query plans are single-node-type"
         ref = generic_outputs(arch, feat, edge_index, mask, list(query), "node", node_type,
                               edge_type, node_type_names, edge_type_names, padded_dims,
-                              edge_weight=edge_weight, edge_attr=edge_attr)
-        got = plan.forward(engine.pack_masks(mask))[:, :len(query)]
+                              edge_weight=edge_weight, edge_attr=edge_attr, **ckw)
+        got = plan.forward(engine.pack_masks(mask))[:, :ref.shape[1]]
         err = (ref - got).abs().max().item()
         return err <= tol * max(1.0, ref.abs().max().item()), err
     ref = generic_outputs(arch, feat, edge_index, mask, query, "node", node_type, edge_type,
                           node_type_names, edge_type_names, padded_dims, q4=not multi,
-                          edge_weight=edge_weight, edge_attr=edge_attr)
+                          edge_weight=edge_weight, edge_attr=edge_attr, **ckw)
     bits = engine.pack_masks(mask)
-    got = plan.forward(bits)[:, 0]
+    got = plan.forward(bits)
+    got = got if ref.dim() == 2 else got[:, 0]
     if multi:  # per-copy outputs on both sides (zero for copies without edges)
         got = torch.where(empty_copy_rows(bits, S, edge_index), torch.zeros_like(got), got)
     err = (ref - got).abs().max().item()

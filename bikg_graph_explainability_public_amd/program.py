@@ -129,6 +129,15 @@ class ModelProgram:
     # compiled for a graph with edge features (compile_arch(edge_attr=True)): every conv is a
     # GINEConv; the plan then needs the attribute rows
     edge_featured: bool = False
+    # a classifier's last unit, nn.Softmax / nn.LogSoftmax over the class dimension: None |
+    # "softmax" | "log_softmax" over the columns of the last head layer (headless: the last conv),
+    # which then carries no activation of its own; the class readout (xpgnn.h, xpg_class_out)
+    out_norm: Optional[str] = None
+
+    @property
+    def n_classes(self):
+        """Output columns C: the last head layer's, or the last conv's of a headless program."""
+        return int(self.head[-1].weight.shape[0]) if self.head else int(self.convs[-1].f_out)
 
     @property
     def hops(self):
@@ -153,6 +162,13 @@ def _act_name(m):
     if name == "ELU" and getattr(m, "alpha", 1.0) != 1.0:
         raise UnsupportedArch("ELU(alpha != 1)")
     return _ACTS[name]
+
+
+_OUT_NORMS = {"Softmax": "softmax", "LogSoftmax": "log_softmax"}
+
+
+def _is_out_norm(m):
+    return type(m).__name__ in _OUT_NORMS and hasattr(m, "dim")
 
 
 def _is_gat(m):
@@ -279,7 +295,7 @@ def _leaf_units(module, attention=False):
         if _is_gatv2(child) and not attention:
             raise UnsupportedArch("GATv2Conv without the attention opt-in (attention=True)")
         if _is_conv(child, attention) or _is_linear(child) or _act_name(child) is not None \
-                or _is_norm(child):
+                or _is_norm(child) or _is_out_norm(child):
             yield child
         elif type(child).__name__ in _SKIP:
             continue
@@ -711,6 +727,25 @@ def _head_layers(prog, units, i):
     return i
 
 
+def _out_norm(prog, units, i):
+    """nn.Softmax / nn.LogSoftmax as the LAST unit, after a head Linear (or a headless model's last
+    conv) that has no activation of its own: sets prog.out_norm and returns the index past it.  Any
+    other place is left to the caller's "unexpected module order"."""
+    if i != len(units) - 1 or not _is_out_norm(units[i]):
+        return i
+    m = units[i]
+    if m.dim not in (-1, 1):
+        raise UnsupportedArch(f"{type(m).__name__}(dim={m.dim!r}): the class dimension (-1 or 1) only")
+    if prog.n_types > 1:
+        raise UnsupportedArch(f"{type(m).__name__} on a multi-node-type graph")
+    last = prog.head[-1] if prog.head else prog.convs[-1]
+    act = last.act if prog.head or last.post is None else last.post.act
+    if act is not None:
+        raise UnsupportedArch(f"{type(m).__name__} after an activation ({act})")
+    prog.out_norm = _OUT_NORMS[type(m).__name__]
+    return i + 1
+
+
 def _check_widths(prog):
     """Width consistency of the conv layers and the head."""
     prev = prog.convs[0].f_in
@@ -750,8 +785,11 @@ def _compile_pooled(arch, edge_type_names, node_type_names, attention, edge_weig
                               "4-argument call)")
     if prog.n_types > 1:
         raise UnsupportedArch("PooledModel on a multi-node-type program")
+    if prog.out_norm is not None:
+        raise UnsupportedArch("PooledModel encoder ending in Softmax / LogSoftmax")
     units = list(_leaf_units(arch.fc, attention))
     i = _head_layers(prog, units, 0)
+    i = _out_norm(prog, units, i)
     if i != len(units):
         raise UnsupportedArch(f"unexpected module order at {type(units[i]).__name__} in PooledModel.fc")
     _check_widths(prog)
@@ -789,6 +827,8 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
         prog = compile_arch(arch.encoder, edge_type_names, node_type_names, attention)
         if prog.pool is not None:
             raise UnsupportedArch("LinkModel over a pooled encoder")
+        if prog.out_norm is not None:
+            raise UnsupportedArch("LinkModel over an encoder ending in Softmax / LogSoftmax")
         if prog.has_post:
             raise UnsupportedArch("LinkModel over an encoder with post-ops (LayerNorm, residual, "
                                   "BatchNorm after attention)")
@@ -798,6 +838,8 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
         prog = compile_arch(arch.encoder, edge_type_names, node_type_names, attention)
         if not all(any(t.kind == "rel" for t in c.terms) for c in prog.convs):
             raise UnsupportedArch("RelLinkModel needs an encoder of RGCNConv layers")
+        if prog.out_norm is not None:
+            raise UnsupportedArch("RelLinkModel over an encoder ending in Softmax / LogSoftmax")
         prog.link_act = getattr(arch, "act", "identity") or "identity"
         emb = getattr(arch, "rel_emb", None)
         if emb is not None:
@@ -866,6 +908,7 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
     if any(typed) and not all(typed):
         raise UnsupportedArch("a model mixing RGCNConv with another conv kind")
     i = _head_layers(prog, units, i)
+    i = _out_norm(prog, units, i)
     if i != len(units):
         raise UnsupportedArch(f"unexpected module order at {type(units[i]).__name__}")
     _check_widths(prog)

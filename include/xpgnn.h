@@ -633,6 +633,52 @@ int xpg_forward_describe_e(const xpg_forward_plan* plan, const xpg_post_desc* po
                            const xpg_edge_weights* weights, const xpg_edge_feats* feats,
                            int64_t rows, char* buf, size_t n);
 
+/* Class readout (v27 addendum: new symbols only; the version, every struct above and every entry
+ * point above are unchanged).  z[m][0..C) is the network's last linear output of output row m =
+ * (mask row, target), a query node or the one pooled row; C = the last head layer's n_real, or the
+ * last conv layer's f_out of a headless plan.  Output column c of row m:
+ *   NONE:        z[m][c]   (what out_col means; element-wise activations already applied)
+ *   SOFTMAX:     exp(z_c - max_j z_j) / sum_j exp(z_j - max_j z_j)   over the C real columns only
+ *   LOG_SOFTMAX: (z_c - max_j z_j) - log sum_j exp(z_j - max_j z_j)
+ * Padded columns never take part, whatever they hold; C = 1 gives exactly 1.0f / 0.0f.
+ * k_class_out<KIND, ALL>: one row on a power-of-two lane group of one wave (k_post's mapping, one
+ * float4 chunk per lane); the maximum and the sum each cross the group by one xor butterfly, so a
+ * row's result depends on its values and (C, ld) alone, never on M or on its position in the launch.
+ * cls == NULL: each _c entry point is its _e namesake, same results (the _e entry points are that
+ * case of the same code).  With cls, plan->out_col is ignored and y holds rows * n_last values
+ * (col >= 0) or rows * n_last * C values (col == -1: [rows][n_last][C]); {NONE, c} gives bitwise
+ * the output of the plain entry with out_col = c where that entry's tail is the column pick
+ * (k_take_col: the same rows, the same element); where the plain entry computes the column in
+ * k_dense's HEAD epilogue, or takes the rows / fused / wide path, the two differ by float32 rounding.
+ * Host checks, XPG_EINVAL before any launch: kind outside the enum; col outside [-1, C);
+ * edge_masks or edge_dot; tgt_type; SOFTMAX / LOG_SOFTMAX over a last head layer (or headless
+ * last conv layer, its post-op included) that carries an element-wise activation.  A plan with cls
+ * runs on the multi-kernel path only (a forced rows / fused / wide path under XPG_FORWARD_STRICT=1
+ * is refused) with the unfused tail: neither the column pick nor the last head layer goes into a
+ * k_dense epilogue, and k_class_out is launched where k_take_col was.  Post-ops, the pooled
+ * readout, weights and edge features compose unchanged.  xpg_forward_describe_c appends
+ * ` class=k_class_out<kind,one|all>`, e.g. `unfused class=k_class_out<softmax,all>`.  The
+ * workspace is that of the same plan on the multi-kernel path. */
+enum xpg_class_kind { XPG_CLASS_NONE = 0, XPG_CLASS_SOFTMAX = 1, XPG_CLASS_LOG_SOFTMAX = 2 };
+typedef struct xpg_class_out {
+  int32_t kind;            /* enum xpg_class_kind                                         */
+  int32_t col;             /* >= 0: that class; -1: all C classes                         */
+} xpg_class_out;
+int xpg_forward_workspace_c(const xpg_forward_plan* plan, const xpg_post_desc* post,
+                            const xpg_edge_weights* weights, const xpg_edge_feats* feats,
+                            const xpg_class_out* cls, int64_t rows, size_t* bytes);
+int xpg_masked_forward_c(const xpg_forward_plan* plan, const xpg_post_desc* post,
+                         const xpg_edge_weights* weights, const xpg_edge_feats* feats,
+                         const xpg_class_out* cls, const uint32_t* bits, int64_t rows, float* y,
+                         void* workspace, size_t workspace_bytes, xpg_stream_t stream);
+int xpg_forward_describe_c(const xpg_forward_plan* plan, const xpg_post_desc* post,
+                           const xpg_edge_weights* weights, const xpg_edge_feats* feats,
+                           const xpg_class_out* cls, int64_t rows, char* buf, size_t n);
+/* The readout on its own: in [M][ld] fp32 (ld % 4 == 0, 4 <= ld <= 256, 16-byte aligned,
+ * 1 <= n_real <= ld) -> out [M] (col >= 0) or [M][n_real] (col == -1). */
+int xpg_class_out_rows(const float* in, int64_t M, int64_t ld, int64_t n_real, int32_t kind,
+                       int32_t col, float* out, xpg_stream_t stream);
+
 /* Optional per-kernel timing of xpg_masked_forward's wide (full-graph) path (v13): with profiling
  * on, every launch of a profiled kernel is bracketed by two hipEvents on its stream;
  * xpg_profile_read waits for them and returns, per slot, the summed device milliseconds and the
