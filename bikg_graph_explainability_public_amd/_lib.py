@@ -16,6 +16,7 @@ MAX_TERMS = 8
 
 ACT = {None: 0, "identity": 0, "relu": 1, "sigmoid": 2, "tanh": 3, "leaky_relu": 4, "elu": 5}
 TERM = {"gcn": 0, "mean": 1, "root": 2, "att": 3, "sum": 4, "max": 5, "rel": 6, "att2": 7}
+TERM_QKV = 8  # XPG_TERM_QKV (TransformerConv, the v27 addendum); program kind "qkv"
 REL_NORM = {"mean": 0, "sum": 1}
 POOL = {None: 0, "mean": 1, "sum": 2, "max": 3}
 NORM = {None: 0, "layer": 1}

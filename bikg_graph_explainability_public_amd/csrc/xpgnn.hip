@@ -1854,6 +1854,158 @@ __global__ __launch_bounds__(256) void k_agg_att2(Att2Args a) {
   reinterpret_cast<float4*>(a.out + item * a.width)[sub] = make_float4(o[0], o[1], o[2], o[3]);
 }
 
+// ------------------------------------------------------------------------------------ dot-product attention
+// XPG_TERM_QKV (TransformerConv; the rules are in xpgnn.h).  The logit of an edge is
+// <Q[t, h], K[u, h]> / sqrt(head_ch) and the messages are rows of a third table V; the term ends in
+// its own epilogue, + S[t] or the learned gate between S[t] and the aggregate.  Transform-then-
+// aggregate at every depth like ATT2: layer 1 reads the plan's K | V | Q (| S) table, a deeper
+// layer k_dense's output for this call's rows.
+struct QkvArgs {
+  int64_t rows;
+  int n_tgt, n_prev, n_terms;
+  int width;   // f_out_pad (floats, % 32 == 0, <= 256)
+  int chunks;  // width / 4
+  int lanes;   // chunks rounded up to a power of two (8 / 16 / 32 / 64)
+  const int32_t* tgt_prev;
+  const int32_t* tgt_f0;
+  const int32_t* agg_ptr;
+  const int32_t* agg_src;
+  const int32_t* agg_f0;
+  const int32_t* self_mult;
+  const int32_t* f0_node;
+  const uint32_t* bits;
+  int words;
+  int rel[XPG_MAX_TERMS];
+  int heads[XPG_MAX_TERMS];
+  int head_ch[XPG_MAX_TERMS];
+  float scale[XPG_MAX_TERMS];        // 1 / sqrt(head_ch)
+  const float* blk[XPG_MAX_TERMS];   // row i at blk + i * ld: K at +0, V at +width, Q at +2 * width,
+  int root[XPG_MAX_TERMS];           // root: S at +3 * width (layer 1: i = F_0 position; deeper: i =
+  int ld[XPG_MAX_TERMS];             // b * n_prev + position in the previous frontier)
+  const float* gate[XPG_MAX_TERMS];  // [2][width] g_out, g_r; NULL: out + S[t]
+  float* out;  // [rows][n_tgt][width]
+  const float* bias;
+  int act;
+  int f_real;
+};
+
+constexpr int kQkvEB = 4;  // in-edges staged together: two rows (K, V) of each are in flight
+
+// The logits of N source rows at the lane's columns, the per-head sums of q * K[u] (q = the
+// target's query row times the scale), by att2_logits' two rules: with att = q, XR = -0 and slope
+// 1 its product att * leaky_relu(K[u] + XR) is q * K[u] exactly (x + -0 == x and 1 * x == x for
+// every x, which the compiler folds away).
+template <bool ALIGNED, int N>
+__device__ __forceinline__ void qkv_logits(const float4* kr, const float4 q, int H, int C, int lanes, int f0,
+                                           float (*z)[ALIGNED ? 1 : 4]) {
+  att2_logits<ALIGNED, N>(kr, make_float4(-0.f, -0.f, -0.f, -0.f), q, 1.f, H, C, lanes, f0, z);
+}
+
+// Dot-product-attention aggregation of one conv layer, the whole layer in one launch.  The mapping
+// is k_agg_att2's: item = (mask row b, target t) on `lanes` lanes of one wave, lane `sub` owns
+// float4 chunk `sub` (lanes past `chunks` load nothing and add zeros to the exchanges), and every
+// branch and loop bound is the same for all lanes of an item.  Stored self-loops are ordinary
+// entries (self_mult copies with sources K[t], V[t]) and, like every in-edge, take part iff the
+// target is kept; a masked target's row is its term epilogue alone.  The result for (b, t) depends
+// on the plan and mask row b alone; the layer epilogue is k_agg_att2's.
+template <bool L1, bool ALIGNED>
+__global__ __launch_bounds__(256) void k_agg_qkv(QkvArgs a) {
+  constexpr int EB = kQkvEB;
+  constexpr int NS = ALIGNED ? 1 : 4;
+  const int64_t item = blockIdx.x * (int64_t)(256 / a.lanes) + threadIdx.x / a.lanes;
+  const int sub = threadIdx.x & (a.lanes - 1);
+  if (item >= a.rows * a.n_tgt) return;
+  const int64_t b = item / a.n_tgt;
+  const int t = static_cast<int>(item - b * a.n_tgt);
+  const uint32_t* mrow = a.bits + b * a.words;
+  const int t0 = a.tgt_f0[t];
+  const int tp = a.tgt_prev[t];
+  const bool t_on = bit_of(mrow, a.f0_node[t0]);
+  const bool live = sub < a.chunks;
+  const int f0 = sub * 4;
+  float tot[4] = {0.f, 0.f, 0.f, 0.f};
+
+  for (int k = 0; k < a.n_terms; ++k) {
+    const int H = a.heads[k], C = a.head_ch[k], r = a.rel[k];
+    const int* pp = a.agg_ptr + (int64_t)r * (a.n_tgt + 1);
+    const int e0 = pp[t], e1 = t_on ? pp[t + 1] : pp[t];
+    const int n_self = t_on ? a.self_mult[(int64_t)r * a.n_tgt + t] : 0;
+    const int64_t ld = a.ld[k];
+    const int64_t row0 = L1 ? 0 : b * (int64_t)a.n_prev;
+    const int self_pos = L1 ? t0 : tp;
+    const float* kt = a.blk[k] + row0 * ld + f0;  // K rows; V rows sit `width` floats further
+    const float* own = kt + self_pos * ld;
+    float4 q = att2_ld4(live, own + 2 * a.width);
+    const float sc = a.scale[k];
+    q = make_float4(q.x * sc, q.y * sc, q.z * sc, q.w * sc);
+    float m[NS], den[NS], acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      m[s] = -INFINITY;
+      den[s] = 0.f;
+    }
+    if (n_self > 0) {
+      const float4 kr = att2_ld4(live, own);
+      const float4 v = att2_ld4(live, own + a.width);
+      const bool kp = true;
+      float z[1][NS];
+      qkv_logits<ALIGNED, 1>(&kr, q, H, C, a.lanes, f0, z);
+      att2_step<ALIGNED, 1>(&v, &kp, static_cast<float>(n_self), z, m, den, acc);
+    }
+    for (int eb = e0; eb < e1; eb += EB) {
+      int up[EB], nd[EB];
+      bool kp[EB];
+      float4 kr[EB], v[EB];
+#pragma unroll
+      for (int i = 0; i < EB; ++i) {
+        const int e = eb + i < e1 ? eb + i : eb;
+        nd[i] = a.agg_f0[e];
+        up[i] = L1 ? nd[i] : a.agg_src[e];
+      }
+#pragma unroll
+      for (int i = 0; i < EB; ++i) nd[i] = a.f0_node[nd[i]];
+#pragma unroll
+      for (int i = 0; i < EB; ++i) kp[i] = bit_of(mrow, nd[i]) && eb + i < e1;
+#pragma unroll
+      for (int i = 0; i < EB; ++i) {
+        kr[i] = att2_ld4(kp[i] && live, kt + up[i] * ld);
+        v[i] = att2_ld4(kp[i] && live, kt + up[i] * ld + a.width);
+      }
+      if (!(kp[0] || kp[1] || kp[2] || kp[3])) continue;
+      float z[EB][NS];
+      qkv_logits<ALIGNED, EB>(kr, q, H, C, a.lanes, f0, z);
+      att2_step<ALIGNED, EB>(v, kp, 1.f, z, m, den, acc);
+    }
+    float o[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = acc[j] * (1.f / (den[ALIGNED ? 0 : j] + 1e-16f));
+    if (a.root[k]) {  // the term's epilogue: + S[t], or the gate between S[t] and the aggregate
+      const float4 s4 = att2_ld4(live, own + 3 * a.width);
+      const float xr[4] = {s4.x, s4.y, s4.z, s4.w};
+      if (a.gate[k]) {
+        const float4 go = att2_ld4(live, a.gate[k] + f0);
+        const float4 gr = att2_ld4(live, a.gate[k] + a.width + f0);
+        float s = (go.x * o[0] + go.y * o[1]) + (go.z * o[2] + go.w * o[3]);
+        s += (gr.x * xr[0] + gr.y * xr[1]) + (gr.z * xr[2] + gr.w * xr[3]);
+        s = att2_xor_sum(s, a.lanes);  // over the whole row: every lane of the item ends with the same bits
+        const float g = 1.f / (1.f + __expf(-s));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = g * xr[j] + (1.f - g) * o[j];
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] += xr[j];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) tot[j] += o[j];
+  }
+  if (!live) return;
+  float o[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) o[j] = (f0 + j < a.f_real) ? act_apply(tot[j] + a.bias[f0 + j], a.act) : 0.f;
+  reinterpret_cast<float4*>(a.out + item * a.width)[sub] = make_float4(o[0], o[1], o[2], o[3]);
+}
+
 // ------------------------------------------------------------------------------------ typed relations
 // XPG_TERM_REL (RGCNConv / FastRGCNConv; the rules are in xpgnn.h): one term for every relation of
 // the plan.  A kernel of its own: k_agg walks its terms with one pointer pair per (term, target),
@@ -7157,9 +7309,15 @@ bool layer_has_att2(const xpg_layer_desc& ly) {
     if (ly.terms[k].kind == XPG_TERM_ATT2) return true;
   return false;
 }
+// dot-product attention (XPG_TERM_QKV, the v27 addendum): layers of their own on the same path
+bool layer_has_qkv(const xpg_layer_desc& ly) {
+  for (int k = 0; k < ly.n_terms && k < XPG_MAX_TERMS; ++k)
+    if (ly.terms[k].kind == XPG_TERM_QKV) return true;
+  return false;
+}
 bool plan_has_attention(const xpg_forward_plan* p) {
   for (int l = 0; l < p->n_layers; ++l)
-    if (layer_has_attention(p->layers[l]) || layer_has_att2(p->layers[l])) return true;
+    if (layer_has_attention(p->layers[l]) || layer_has_att2(p->layers[l]) || layer_has_qkv(p->layers[l])) return true;
   return false;
 }
 // The argument rules of ATT2 layers (xpgnn.h), checked on the host before anything is launched and
@@ -7193,6 +7351,38 @@ int att2_plan_check(const xpg_forward_plan* p) {
   }
   return XPG_OK;
 }
+// The argument rules of QKV layers (xpgnn.h), checked on the host before anything is launched and
+// without reading through any of the plan's device pointers.
+int qkv_plan_check(const xpg_forward_plan* p) {
+  for (int l = 0; l < p->n_layers; ++l) {
+    const xpg_layer_desc& ly = p->layers[l];
+    if (!layer_has_qkv(ly)) continue;
+    XPG_REQ(ly.n_terms >= 1 && ly.n_terms <= XPG_MAX_TERMS, "layer: 1..8 terms");
+    XPG_REQ(!p->edge_masks, "QKV terms do not take edge-mask plans (edge_masks)");
+    XPG_REQ(!ly.tgt_type, "QKV layer: multi-node-type plans (tgt_type) are not taken");
+    XPG_REQ(p->f0_node, "QKV terms need f0_node");
+    XPG_REQ(ly.f_out_pad > 0 && ly.f_out_pad % 32 == 0 && ly.f_out_pad <= 256,
+            "QKV layer: f_out_pad must be 32..256, a multiple of 32");
+    XPG_REQ(l > 0 || !(ly.weight && ly.f_in_pad > 0), "QKV layer 1 does not take the raw form");
+    XPG_REQ(!ly.weight, "QKV layer: weight must be NULL (the terms carry the K / V / Q / S maps)");
+    XPG_REQ(l == 0 || (ly.f_in_pad == p->layers[l - 1].f_out_pad && ly.f_in_pad % 8 == 0),
+            "layer: f_in_pad must equal previous f_out_pad");
+    XPG_REQ(ly.bias, "QKV layer: bias missing");
+    for (int k = 0; k < ly.n_terms; ++k) {
+      const xpg_term_desc& td = ly.terms[k];
+      XPG_REQ(td.kind == XPG_TERM_QKV, "layer: QKV terms cannot be mixed with other kinds");
+      XPG_REQ(td.rel >= 0 && td.rel < p->n_rel, "term: bad relation");
+      XPG_REQ(td.dst_type == -1, "QKV term: dst_type must be -1");
+      XPG_REQ(td.heads >= 1 && td.head_ch >= 1 && (int64_t)td.heads * td.head_ch <= ly.f_out_pad,
+              "QKV term: heads * head_ch must fit the layer's output width");
+      XPG_REQ(td.n_slices == 3 || td.n_slices == 4, "QKV term: n_slices must be 3 (K, V, Q) or 4 (and S)");
+      XPG_REQ(!td.att_src || td.n_slices == 4, "QKV term: a gate (att_src) needs the S block (n_slices == 4)");
+      XPG_REQ(td.table, "QKV term: missing table");
+      XPG_REQ(l == 0 || td.coef, "QKV term: a deeper layer needs coef (the biases)");
+    }
+  }
+  return XPG_OK;
+}
 // typed-relation (XPG_TERM_REL, v26) layers run on the multi-kernel path only
 bool layer_has_rel(const xpg_layer_desc& ly) {
   for (int k = 0; k < ly.n_terms && k < XPG_MAX_TERMS; ++k)
@@ -7210,7 +7400,9 @@ bool plan_needs_degree(const xpg_forward_plan* p) {
   if (plan_has_rel(p)) return false;  // edge masks included: the EM kernels test the edge columns
   for (int l = 0; l < p->n_layers; ++l)
     for (int k = 0; k < p->layers[l].n_terms && k < XPG_MAX_TERMS; ++k)
-      if (p->layers[l].terms[k].kind != XPG_TERM_ATT && p->layers[l].terms[k].kind != XPG_TERM_ATT2) return true;
+      if (p->layers[l].terms[k].kind != XPG_TERM_ATT && p->layers[l].terms[k].kind != XPG_TERM_ATT2 &&
+          p->layers[l].terms[k].kind != XPG_TERM_QKV)
+        return true;
   return p->edge_masks != 0;
 }
 // SUM / MAX terms (v25) and the raw (aggregate-then-transform) layer 1 that MAX needs there: the
@@ -7264,6 +7456,7 @@ int layout_ws(const xpg_forward_plan* p, int64_t rows, WsLayout* L, const xpg_ed
   XPG_REQ(p && p->n_layers >= 1 && p->n_layers <= 64, "plan: 1..64 conv layers required");
   if (const int rc = pool_plan_check(p)) return rc;
   if (const int rc = att2_plan_check(p)) return rc;
+  if (const int rc = qkv_plan_check(p)) return rc;
   size_t off = 0;
   L->kin = off;  // REL plans read no degrees: no region (n_rel can be in the hundreds)
   if (!plan_has_rel(p)) off += align_up(sizeof(float) * (size_t)rows * p->n_rel * deg_pitch(p));
@@ -7275,6 +7468,15 @@ int layout_ws(const xpg_forward_plan* p, int64_t rows, WsLayout* L, const xpg_ed
     if (layer_has_att2(ly)) {  // transform-then-aggregate: no dense input, no scores
       if (l > 0) {             // XL | XR of every previous-frontier row, per term
         size_t x = sizeof(float) * (size_t)rows * p->layers[l - 1].n_tgt * 2 * ly.n_terms * ly.f_out_pad;
+        xlr_max = x > xlr_max ? x : xlr_max;
+      }
+      continue;
+    }
+    if (layer_has_qkv(ly)) {  // likewise; K | V | Q (| S) of every previous-frontier row, per term
+      if (l > 0) {
+        size_t nb = 0;
+        for (int k = 0; k < ly.n_terms; ++k) nb += ly.terms[k].n_slices;
+        size_t x = sizeof(float) * (size_t)rows * p->layers[l - 1].n_tgt * nb * ly.f_out_pad;
         xlr_max = x > xlr_max ? x : xlr_max;
       }
       continue;
@@ -7302,7 +7504,7 @@ int layout_ws(const xpg_forward_plan* p, int64_t rows, WsLayout* L, const xpg_ed
   off += align_up(hmax);
   L->score = off;  // attention layers' score pre-pass (0 bytes for plans without ATT terms)
   off += align_up(score_max);
-  L->xlr = off;  // ATT2 layers past the first: the transformed rows (0 bytes for plans without them)
+  L->xlr = off;  // ATT2 / QKV layers past the first: the transformed rows (0 bytes for plans without them)
   off += align_up(xlr_max);
   L->ctl = off;  // the rows forward's block-scheduling counters (zeroed before each launch)
   off += align_up(sizeof(int) * 32);
@@ -7597,6 +7799,79 @@ int launch_att2_layer(const xpg_forward_plan* p, int l, const uint32_t* bits, in
   } else {
     if (aligned) hipLaunchKernelGGL((k_agg_att2<false, true>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((k_agg_att2<false, false>), grid, block, 0, st, a);
+  }
+  XPG_LAUNCHED();
+  return XPG_OK;
+}
+
+// One dot-product-attention layer (every term XPG_TERM_QKV, qkv_plan_check passed), finished into
+// out: layer 1 is one k_agg_qkv<true> launch on the plan's K | V | Q (| S) tables; a deeper layer
+// first transforms every previous-frontier row of this call (k_dense, biases from coef, no
+// activation) into the xlr region, per term one [rows * n_prev][n_slices * f_out_pad] block, in as
+// many launches as k_dense's 256 columns need, then aggregates.  No dense launch follows.
+int launch_qkv_layer(const xpg_forward_plan* p, int l, const uint32_t* bits, int64_t rows, const float* hprev,
+                     float* xlr, float* out, hipStream_t st) {
+  const xpg_layer_desc& ly = p->layers[l];
+  QkvArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.rows = rows;
+  a.n_tgt = ly.n_tgt;
+  a.n_prev = l == 0 ? p->n0 : p->layers[l - 1].n_tgt;
+  a.n_terms = ly.n_terms;
+  a.width = ly.f_out_pad;
+  a.chunks = a.width / 4;
+  a.lanes = a.chunks <= 8 ? 8 : a.chunks <= 16 ? 16 : a.chunks <= 32 ? 32 : 64;
+  a.tgt_prev = ly.tgt_prev;
+  a.tgt_f0 = ly.tgt_f0;
+  a.agg_ptr = ly.agg_ptr;
+  a.agg_src = ly.agg_src;
+  a.agg_f0 = ly.agg_f0;
+  a.self_mult = ly.self_mult;
+  a.f0_node = p->f0_node;
+  a.bits = bits;
+  a.words = words_of(p->cols);
+  a.out = out;
+  a.bias = ly.bias;
+  a.act = ly.act;
+  a.f_real = ly.f_out;
+  bool aligned = true;
+  const int64_t n_in = rows * a.n_prev;  // rows of the layer's input
+  const int64_t np = ly.f_out_pad;
+  const int per = static_cast<int>(256 / np);  // blocks per k_dense launch
+  float* blk = xlr;
+  for (int k = 0; k < ly.n_terms; ++k) {
+    const xpg_term_desc& td = ly.terms[k];
+    const int hl = td.head_ch / 4, nb = td.n_slices;
+    aligned = aligned && td.head_ch % 4 == 0 && (hl & (hl - 1)) == 0;
+    a.rel[k] = td.rel;
+    a.heads[k] = td.heads;
+    a.head_ch[k] = td.head_ch;
+    a.scale[k] = td.neg_slope;
+    a.root[k] = nb == 4;
+    a.gate[k] = td.att_src;
+    a.ld[k] = static_cast<int>(nb * np);
+    if (l == 0) {
+      a.blk[k] = td.table;
+      continue;
+    }
+    for (int s = 0; s < nb; s += per) {
+      const int64_t n = (nb - s < per ? nb - s : per) * np;
+      if (const int rc = launch_dense(hprev, n_in, ly.f_in_pad, td.table + s * np * ly.f_in_pad, ly.f_in_pad,
+                                      ly.f_in_pad, td.coef + s * np, n, n, XPG_ACT_NONE, blk + s * np, nb * np, st))
+        return rc;
+    }
+    a.blk[k] = blk;
+    blk += n_in * nb * np;
+  }
+  const int64_t items = rows * ly.n_tgt;
+  if (items == 0) return XPG_OK;
+  const dim3 grid(static_cast<unsigned>(cdiv(items, 256 / a.lanes))), block(256);
+  if (l == 0) {
+    if (aligned) hipLaunchKernelGGL((k_agg_qkv<true, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_agg_qkv<true, false>), grid, block, 0, st, a);
+  } else {
+    if (aligned) hipLaunchKernelGGL((k_agg_qkv<false, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_agg_qkv<false, false>), grid, block, 0, st, a);
   }
   XPG_LAUNCHED();
   return XPG_OK;
@@ -9140,9 +9415,10 @@ int xpg_masked_forward_c(const xpg_forward_plan* p, const xpg_post_desc* post, c
   bool fuse_out = false;
   // A pooled plan's head follows the readout, which is no dense layer: its last head layer is
   // fused only into the head layer before it (k_dense HEAD on M = rows rows, as for one query).
-  // Nor does an ATT2 last layer end in a dense launch (k_agg_att2 finishes the layer itself).
+  // Nor does an ATT2 or QKV last layer end in a dense launch (its kernel finishes the layer itself).
   const int pool = plan_pool(p);
-  const bool last_att2 = layer_has_att2(p->layers[p->n_layers - 1]);
+  const bool last_att2 =
+      layer_has_att2(p->layers[p->n_layers - 1]) || layer_has_qkv(p->layers[p->n_layers - 1]);
   // Nor may a last conv layer with a post-op take the column pick or the first head layer into its
   // k_dense epilogue: the post-op runs between the two.
   const bool last_post = has_post && post_any(post[p->n_layers - 1]);
@@ -9214,6 +9490,12 @@ int xpg_masked_forward_c(const xpg_forward_plan* p, const xpg_post_desc* post, c
     if (layer_has_att2(ly)) {
       rc = launch_att2_layer(p, l, bits, rows, l == 0 ? nullptr : reinterpret_cast<const float*>(ws + L.h[l - 1]),
                              reinterpret_cast<float*>(ws + L.xlr), reinterpret_cast<float*>(ws + L.h[l]), st);
+      if (rc) return rc;
+      return XPG_OK;
+    }
+    if (layer_has_qkv(ly)) {
+      rc = launch_qkv_layer(p, l, bits, rows, l == 0 ? nullptr : reinterpret_cast<const float*>(ws + L.h[l - 1]),
+                            reinterpret_cast<float*>(ws + L.xlr), reinterpret_cast<float*>(ws + L.h[l]), st);
       if (rc) return rc;
       return XPG_OK;
     }

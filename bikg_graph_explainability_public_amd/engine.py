@@ -966,6 +966,15 @@ def _pad_table(T, n):
     return out
 
 
+def _qkv_blocks(term):
+    """The (weight, bias) blocks of a "qkv" term in the order the engine stores them: K, V, Q and,
+    with root_weight, S."""
+    blocks = [(term.weight, term.bias_l), (term.weight_v, term.bias_v), (term.weight_q, term.bias_q)]
+    if term.weight_s is not None:
+        blocks.append((term.weight_s, term.bias_s))
+    return blocks
+
+
 # ForwardPlan drops the relation terms of other destination types from a layer whose targets
 # share one node type (they add exactly 0); False keeps every term (the parity suite's reference)
 PLAN_DROP_OTHER_TYPES = True
@@ -1127,6 +1136,12 @@ class ForwardPlan:
             if att2 and (self.edge_masks or program.n_types > 1):
                 raise ValueError("dynamic-attention terms on edge-mask or multi-node-type plans "
                                  "are not supported")
+            qkv = any(t.kind == "qkv" for t in terms)
+            if qkv and not all(t.kind == "qkv" for t in terms):
+                raise ValueError("a conv layer mixing dot-product attention with other terms is not supported")
+            if qkv and (self.edge_masks or program.n_types > 1):
+                raise ValueError("dot-product-attention terms on edge-mask or multi-node-type plans "
+                                 "are not supported")
             if self.edge_masks and any(t.kind in ("sum", "max") for t in terms):
                 raise ValueError("sum / max terms on edge-mask plans are not supported")
             rel = [t for t in terms if t.kind == "rel"]
@@ -1211,7 +1226,7 @@ class ForwardPlan:
             else:
                 ld.tgt_type = None
             for k, term in enumerate(terms):
-                ld.terms[k].kind = TERM[term.kind]
+                ld.terms[k].kind = _lib.TERM_QKV if term.kind == "qkv" else TERM[term.kind]
                 ld.terms[k].rel = term.rel
                 ld.terms[k].dst_type = term.dst_type
                 if term.kind == "att":
@@ -1228,6 +1243,24 @@ class ForwardPlan:
                         lambda term=term, f_out_pad=f_out_pad: _pad_vec(term.att.reshape(-1), f_out_pad, device))
                     self._keep.append(att_p)
                     ld.terms[k].att_src = att_p.data_ptr()
+                if term.kind == "qkv":
+                    ld.terms[k].heads, ld.terms[k].head_ch = term.heads, term.head_ch
+                    # the logit scale 1 / sqrt(head_ch), rounded once from fp64, travels in neg_slope
+                    ld.terms[k].neg_slope = float(np.float32(1.0 / np.sqrt(np.float64(term.head_ch))))
+                    ld.terms[k].self_loops = 0
+                    ld.terms[k].dst_type = -1
+                    ld.terms[k].n_slices = len(_qkv_blocks(term))
+                    ld.terms[k].att_dst = None
+                    if term.gate_out is not None:
+                        gate = self._program_tensor(
+                            program, ("qkv_gate", li, id(term)),
+                            lambda term=term, f_out_pad=f_out_pad: torch.stack(
+                                [_pad_vec(term.gate_out, f_out_pad, device),
+                                 _pad_vec(term.gate_r, f_out_pad, device)]).contiguous())
+                        self._keep.append(gate)
+                        ld.terms[k].att_src = gate.data_ptr()
+                    else:
+                        ld.terms[k].att_src = None
                 if term.kind == "rel":
                     ld.terms[k].n_slices = self.n_rel if li == 0 else term.slices
                     ld.terms[k].norm = REL_NORM[term.norm]
@@ -1258,6 +1291,14 @@ class ForwardPlan:
                                        f_out_pad)
                         self._keep += [XL, XR]
                         ld.terms[k].table, ld.terms[k].att_dst = XL.data_ptr(), XR.data_ptr()
+                        continue
+                    if term.kind == "qkv":
+                        # K | V | Q (| S) of the F_0 nodes with their biases, one f_out_pad-wide
+                        # block each, shared by every mask row; padded columns 0
+                        T = torch.cat([_pad_table(dense(X0, w.to(device), _dev(b, device)), f_out_pad)
+                                       for w, b in _qkv_blocks(term)], dim=1).contiguous()
+                        self._keep.append(T)
+                        ld.terms[k].table = T.data_ptr()
                         continue
                     T = dense(X0, term.weight.to(device), None, None)
                     Tp = torch.zeros((n0, f_out_pad), dtype=torch.float32, device=device)
@@ -1295,6 +1336,23 @@ class ForwardPlan:
                     self._keep += [w2, b2]
                     ld.terms[k].table, ld.terms[k].coef = w2.data_ptr(), b2.data_ptr()
                     ld.terms[k].n_slices = w2.shape[0]  # 1: shared weights
+            elif qkv:
+                # transform-then-aggregate: per term the stacked [W_k; W_v; W_q (; W_s)] and their
+                # biases, zero-padded; the layer itself has no weight
+                ld.weight = None
+                for k, term in enumerate(terms):
+                    def make_qkv(term=term, prev_pad=prev_pad, f_out_pad=f_out_pad):
+                        blocks = _qkv_blocks(term)
+                        w = torch.zeros((len(blocks), f_out_pad, prev_pad), dtype=torch.float32, device=device)
+                        b = torch.zeros((len(blocks), f_out_pad), dtype=torch.float32, device=device)
+                        for i, (wi, bi) in enumerate(blocks):
+                            w[i, :wi.shape[0], :wi.shape[1]] = wi.to(device)
+                            if bi is not None:
+                                b[i, :bi.shape[0]] = bi.to(device)
+                        return w, b
+                    w4, b4 = self._program_tensor(program, ("qkv_w", li, id(term)), make_qkv)
+                    self._keep += [w4, b4]
+                    ld.terms[k].table, ld.terms[k].coef = w4.data_ptr(), b4.data_ptr()
             elif att:
                 # one f_in_pad-wide slice of the dense input per (term, head): head h's rows of
                 # W_src in slice (k, h), zeros elsewhere, so the layer stays aggregate-then-transform

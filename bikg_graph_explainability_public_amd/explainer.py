@@ -164,8 +164,8 @@ class Explainer:
 
     @property
     def attention_engine(self):
-        """params["attention_engine"] (default False): compile GATConv relations to the HIP
-        engine's attention kernels instead of running such archs on the generic torch path."""
+        """params["attention_engine"] (default False): compile GATConv, GATv2Conv and
+        TransformerConv relations to the HIP engine's attention kernels instead of running such archs on the generic torch path."""
         return bool(self.params.get("attention_engine", False))
 
     @property

@@ -1,5 +1,5 @@
-"""PyG-2.0.4-compatible graph layers (GCNConv, SAGEConv, GraphConv, GINConv, GATConv, RGCNConv,
-HeteroConv, Linear).
+"""PyG-2.0.4-compatible graph layers (GCNConv, SAGEConv, GraphConv, GINConv, GATConv, GATv2Conv,
+TransformerConv, RGCNConv, HeteroConv, Linear).
 
 PyTorch Geometric is not available on ROCm boxes here; these modules carry the same
 `state_dict` keys as torch_geometric 2.0.4 (`lin.weight` / `bias` for GCNConv, `lin_l.*` /
@@ -425,6 +425,72 @@ class GATv2Conv(MessagePassing):
                 f"share_weights={self.share_weights}")
 
 
+class TransformerConv(MessagePassing):
+    """TransformerConv (PyG 2.0.4, the UniMP layer), scaled dot-product attention: Q = lin_query(x),
+    K = lin_key(x), V = lin_value(x) viewed as [n, heads, out_channels]; logit of edge (u -> t),
+    head h: <Q[t, h], K[u, h]> / sqrt(out_channels); softmax over each target's in-edges (exactly
+    the given edges: no self-loops are added or removed; a target without an in-edge gets 0);
+    out[t, h] = sum alpha V[u, h]; heads concatenated (or averaged).  With `root_weight`
+    x_r = lin_skip(x)[t] is added, or, with `beta`, mixed in through the learned gate
+    g = sigmoid(lin_beta([out, x_r, out - x_r])): out = g x_r + (1 - g) out.  There is no separate
+    bias parameter; `bias` is lin_skip's.  State-dict keys lin_key.* / lin_query.* / lin_value.* /
+    lin_skip.* / lin_beta.weight.  Archs using it run on the generic torch path unless the
+    attention opt-in is set (Explainer params["attention_engine"] = True,
+    program.compile_arch(..., attention=True)): then the engine compiles it to its dot-product
+    attention HIP kernel (concat=True, or concat=False with one head; no edge_dim; Tensor input,
+    int in_channels)."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, beta=False, dropout=0.0,
+                 edge_dim=None, bias=True, root_weight=True, **kwargs):
+        super().__init__()
+        if not isinstance(in_channels, int):
+            raise NotImplementedError("TransformerConv takes an int in_channels (Tensor input)")
+        if edge_dim is not None:
+            raise NotImplementedError("TransformerConv with edge_dim is not supported")
+        self.in_channels, self.out_channels, self.heads = in_channels, out_channels, heads
+        self.concat, self.dropout, self.edge_dim = concat, dropout, None
+        self.root_weight, self.beta = root_weight, bool(beta and root_weight)
+        self.lin_key = Linear(in_channels, heads * out_channels)
+        self.lin_query = Linear(in_channels, heads * out_channels)
+        self.lin_value = Linear(in_channels, heads * out_channels)
+        self.lin_edge = None
+        skip = heads * out_channels if concat else out_channels
+        self.lin_skip = Linear(in_channels, skip, bias=bias)
+        self.lin_beta = Linear(3 * skip, 1, bias=False) if self.beta else None
+
+    def forward(self, x, edge_index):
+        H, C = self.heads, self.out_channels
+        q = self.lin_query(x).view(-1, H, C)
+        k = self.lin_key(x).view(-1, H, C)
+        v = self.lin_value(x).view(-1, H, C)
+        ei = edge_index.long()
+        src, dst = ei[0], ei[1]
+        n = q.size(0)
+        alpha = (q[dst] * k[src]).sum(-1) / math.sqrt(C)                         # [E, H]
+        idx = dst.unsqueeze(1).expand(-1, H)
+        amax = torch.zeros((n, H), dtype=alpha.dtype, device=alpha.device).scatter_reduce(
+            0, idx, alpha, reduce="amax", include_self=False)
+        ex = (alpha - amax[dst]).exp()
+        den = torch.zeros((n, H), dtype=alpha.dtype, device=alpha.device).index_add_(0, dst, ex)
+        alpha = ex / (den[dst] + 1e-16)
+        alpha = F.dropout(alpha, p=self.dropout, training=self.training)
+        out = torch.zeros((n, H, C), dtype=v.dtype, device=v.device)
+        out.index_add_(0, dst, v[src] * alpha.unsqueeze(-1))
+        out = out.reshape(n, H * C) if self.concat else out.mean(dim=1)
+        if self.root_weight:
+            x_r = self.lin_skip(x)
+            if self.lin_beta is not None:
+                g = torch.sigmoid(self.lin_beta(torch.cat([out, x_r, out - x_r], dim=-1)))
+                out = g * x_r + (1 - g) * out
+            else:
+                out = out + x_r
+        return out
+
+    def extra_repr(self):
+        return (f"{self.in_channels}, {self.out_channels}, heads={self.heads}, beta={self.beta}, "
+                f"root_weight={self.root_weight}")
+
+
 class RGCNConv(MessagePassing):
     """RGCNConv (PyG 2.0.4, dense features): out[t] = sum_r AGG_{e = (u -> t), type(e) = r} x_u W_r
     + x_t root + bias, W_r [in, out] (not Linear's [out, in]).  `aggr` = mean (the default; per
@@ -562,15 +628,20 @@ class ConvStack(nn.Module):
     wraps each conv in HeteroConv over the given edge types (single node type).  "gat":
     GATConv layers with `heads[i]` concatenated heads of dims[i + 1] channels (default all 1), so
     layer i reads dims[i] * heads[i - 1] columns and the head reads dims[-1] * heads[-1].
-    "gatv2": the same with GATv2Conv layers; `share_weights` is handed to them."""
+    "gatv2": the same with GATv2Conv layers; `share_weights` is handed to them.  "transformer":
+    the same widths with TransformerConv layers; `beta` and `root_weight` are handed to them."""
 
     def __init__(self, kind, dims, fc_dims, hetero_rels=None, final_act="sigmoid", heads=None,
-                 add_self_loops=True, share_weights=False, edge_dim=None):
+                 add_self_loops=True, share_weights=False, edge_dim=None, beta=False, root_weight=True):
         super().__init__()
         n_conv = len(dims) - 1
         if edge_dim is not None and kind != "gine":
             raise ValueError("edge_dim applies to kind='gine' only")
-        if kind in ("gat", "gatv2"):
+        if beta and kind != "transformer":
+            raise ValueError("beta applies to kind='transformer' only")
+        if not root_weight and kind != "transformer":
+            raise ValueError("root_weight applies to kind='transformer' only")
+        if kind in ("gat", "gatv2", "transformer"):
             heads = [1] * n_conv if heads is None else [int(h) for h in heads]
             if len(heads) != n_conv:
                 raise ValueError("heads must give one entry per conv layer")
@@ -579,6 +650,8 @@ class ConvStack(nn.Module):
 
             def mk(f_in, f_out, i):
                 f_in = f_in * (heads[i - 1] if i else 1)
+                if kind == "transformer":
+                    return TransformerConv(f_in, f_out, heads=heads[i], beta=beta, root_weight=root_weight)
                 if kind == "gatv2":
                     return GATv2Conv(f_in, f_out, heads=heads[i], add_self_loops=add_self_loops,
                                      share_weights=share_weights)
@@ -644,7 +717,8 @@ class BlockStack(nn.Module):
     normally block 0, takes no skip), else h = z.
 
     `kind`: every ConvStack kind.  `norm`: None, "batch" (torch.nn.BatchNorm1d(width)) or "layer"
-    (torch.nn.LayerNorm(width)); `width` = dims[i + 1] * heads[i] for "gat" / "gatv2".  kind "gin"
+    (torch.nn.LayerNorm(width)); `width` = dims[i + 1] * heads[i] for "gat" / "gatv2" /
+    "transformer" (whose `beta` and `root_weight` are handed to TransformerConv).  kind "gin"
     (and "gine", with `edge_dim` and forward's `edge_attr=`) with norm "batch" is the textbook GIN
     block GINConv(Sequential(Linear, BatchNorm1d, ReLU, Linear)) with no norm after the conv; with norm "layer" the LayerNorm follows the conv.
 
@@ -653,14 +727,18 @@ class BlockStack(nn.Module):
     LayerNorm and the skip are the layer's post-op (k_post in csrc/xpgnn.hip)."""
 
     def __init__(self, kind, dims, fc_dims, norm=None, residual=False, final_act="sigmoid", heads=None,
-                 add_self_loops=True, share_weights=False, edge_dim=None):
+                 add_self_loops=True, share_weights=False, edge_dim=None, beta=False, root_weight=True):
         super().__init__()
         if norm not in (None, "batch", "layer"):
             raise ValueError("BlockStack norm must be None, 'batch' or 'layer'")
         if edge_dim is not None and kind != "gine":
             raise ValueError("edge_dim applies to kind='gine' only")
+        if beta and kind != "transformer":
+            raise ValueError("beta applies to kind='transformer' only")
+        if not root_weight and kind != "transformer":
+            raise ValueError("root_weight applies to kind='transformer' only")
         n_conv = len(dims) - 1
-        attn = kind in ("gat", "gatv2")
+        attn = kind in ("gat", "gatv2", "transformer")
         if attn:
             heads = [1] * n_conv if heads is None else [int(h) for h in heads]
             if len(heads) != n_conv:
@@ -693,7 +771,10 @@ class BlockStack(nn.Module):
             f_in, f_out = dims[i], dims[i + 1]
             if attn:
                 f_in, width = f_in * (heads[i - 1] if i else 1), f_out * heads[i]
-                if kind == "gatv2":
+                if kind == "transformer":
+                    convs.append(TransformerConv(f_in, f_out, heads=heads[i], beta=beta,
+                                                 root_weight=root_weight))
+                elif kind == "gatv2":
                     convs.append(GATv2Conv(f_in, f_out, heads=heads[i], add_self_loops=add_self_loops,
                                            share_weights=share_weights))
                 else:

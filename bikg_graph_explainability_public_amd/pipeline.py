@@ -135,8 +135,8 @@ def build_plan(arch, feat, edge_index, queries, node_type=None, edge_type=None,
                node_type_names=None, edge_type_names=None, padded_dims=None, module_state=None,
                attention=False, edge_weight=None, edge_attr=None, out_col=None, classes=None):
     """ForwardPlan for `arch` on the (sub)graph, or None when the engine cannot run it.
-    `attention=True` (opt-in, Explainer params["attention_engine"]) also compiles GATConv
-    relations, which otherwise run on the generic torch path.
+    `attention=True` (opt-in, Explainer params["attention_engine"]) also compiles GATConv,
+    GATv2Conv and TransformerConv relations, which otherwise run on the generic torch path.
 
     A stack of RGCNConv / FastRGCNConv layers (the 4-argument call arch(x, edge_index, node_types,
     edge_types), model.py:102-112) takes `edge_type` as its relations, with or without

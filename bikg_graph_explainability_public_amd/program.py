@@ -3,7 +3,7 @@
 The reference treats `arch` as a black box and calls `arch(feat, edge_index)` on the B-fold
 union graph (model.py:62-116).  The engine instead recognises the supported module family —
 GCNConv / SAGEConv (mean, add, max) / GraphConv / GINConv / HeteroConv(sum) conv layers, stacks of RGCNConv / FastRGCNConv on a
-typed-edge graph (and, with `attention=True`, GATConv and GATv2Conv),
+typed-edge graph (and, with `attention=True`, GATConv, GATv2Conv and TransformerConv),
 each optionally followed by an elementwise activation, then Linear layers with activations (the
 layout of tests/test_utils.py:10-83 and the notebooks) — and lowers it to:
 
@@ -40,7 +40,7 @@ class UnsupportedArch(ValueError):
 
 @dataclass
 class Term:
-    kind: str          # "gcn" | "mean" | "sum" | "max" | "root" | "att" | "rel" | "att2"
+    kind: str          # "gcn" | "mean" | "sum" | "max" | "root" | "att" | "rel" | "att2" | "qkv"
     rel: int           # relation index (ignored for root and rel)
     weight: torch.Tensor  # [f_out, f_in] (att: W_src, [heads * head_ch, f_in]; rel: [slices, f_out, f_in])
     dst_type: int = -1    # multi-node-type: destination node type of the relation
@@ -58,6 +58,20 @@ class Term:
     bias_l: Optional[torch.Tensor] = None      # lin_l.bias [heads * head_ch] (inside the messages)
     bias_r: Optional[torch.Tensor] = None      # lin_r.bias
     att: Optional[torch.Tensor] = None         # [heads, head_ch]
+    # kind "qkv" (TransformerConv, PyG 2.0.4): one term per relation; weight = W_key, bias_l =
+    # lin_key.bias, heads / head_ch as for "att"; the logit of (u -> t) is <Q[t], K[u]> / sqrt(head_ch),
+    # the messages are rows of V; the edge set is the given edges (self_loops False)
+    weight_v: Optional[torch.Tensor] = None    # lin_value.weight [heads * head_ch, f_in]
+    weight_q: Optional[torch.Tensor] = None    # lin_query.weight
+    weight_s: Optional[torch.Tensor] = None    # lin_skip.weight; None: root_weight=False
+    bias_v: Optional[torch.Tensor] = None
+    bias_q: Optional[torch.Tensor] = None
+    bias_s: Optional[torch.Tensor] = None      # lin_skip.bias (None with bias=False)
+    # the gate of beta=True, sigmoid(<gate_out, out> + <gate_r, x_r>): lin_beta.weight = [w1 | w2 |
+    # w3] over [out, x_r, out - x_r] folded to gate_out = w1 + w3, gate_r = w2 - w3 (fp64, rounded
+    # once); both None: out + x_r
+    gate_out: Optional[torch.Tensor] = None    # [heads * head_ch]
+    gate_r: Optional[torch.Tensor] = None
     # kind "rel" (RGCNConv / FastRGCNConv, PyG 2.0.4): one term per conv layer, over every edge
     # type of the graph.  Per relation r the mean (norm "mean": over that relation's kept in-edges,
     # 0 without one) or sum (norm "sum") A_r of the source rows; the term adds sum_s B_s weight[s]^T
@@ -181,6 +195,11 @@ def _is_gatv2(m):
         hasattr(m, a) for a in ("lin_l", "lin_r", "att", "heads", "out_channels"))
 
 
+def _is_transformer(m):
+    return type(m).__name__ == "TransformerConv" and all(
+        hasattr(m, a) for a in ("lin_key", "lin_query", "lin_value", "heads", "out_channels"))
+
+
 def _is_graphconv(m):
     return type(m).__name__ == "GraphConv" and hasattr(m, "lin_rel") and hasattr(m, "lin_root")
 
@@ -202,7 +221,7 @@ def _is_rgcn(m):
 
 def _is_conv(m, attention=False):
     return type(m).__name__ in ("GCNConv", "SAGEConv", "HeteroConv") or _is_graphconv(m) or _is_gin(m) \
-        or _is_gine(m) or _is_rgcn(m) or (attention and (_is_gat(m) or _is_gatv2(m)))
+        or _is_gine(m) or _is_rgcn(m) or (attention and (_is_gat(m) or _is_gatv2(m) or _is_transformer(m)))
 
 
 def _is_linear(m):
@@ -294,6 +313,8 @@ def _leaf_units(module, attention=False):
     for child in module.children():
         if _is_gatv2(child) and not attention:
             raise UnsupportedArch("GATv2Conv without the attention opt-in (attention=True)")
+        if _is_transformer(child) and not attention:
+            raise UnsupportedArch("TransformerConv without the attention opt-in (attention=True)")
         if _is_conv(child, attention) or _is_linear(child) or _act_name(child) is not None \
                 or _is_norm(child) or _is_out_norm(child):
             yield child
@@ -374,6 +395,42 @@ def _gatv2_terms(conv, rel, bipartite):
     return [term], b, None, Wl.shape[1], H * C
 
 
+def _transformer_terms(conv, rel, bipartite):
+    """One TransformerConv relation as a "qkv" term: the key / value / query maps with their biases,
+    the skip map when root_weight, and the beta gate folded to two vectors.  The conv has no bias
+    of its own, so the layer's is None."""
+    H, C = int(conv.heads), int(conv.out_channels)
+    if not bool(getattr(conv, "concat", True)) and H > 1:
+        raise UnsupportedArch("TransformerConv(concat=False) with several heads")
+    if getattr(conv, "edge_dim", None) is not None or getattr(conv, "lin_edge", None) is not None:
+        raise UnsupportedArch("TransformerConv with edge_dim")
+    if (H * C + 31) // 32 * 32 > 256:
+        raise UnsupportedArch("TransformerConv wider than 256 columns (heads * out_channels, padded to 32)")
+    if bipartite or not isinstance(getattr(conv, "in_channels", 0), int):
+        raise UnsupportedArch("TransformerConv on a bipartite relation / with tuple in_channels")
+    root = bool(getattr(conv, "root_weight", True))
+    lins = [conv.lin_key, conv.lin_value, conv.lin_query] + ([conv.lin_skip] if root else [])
+    if any(_lazy(lin) for lin in lins):
+        raise UnsupportedArch("TransformerConv with uninitialised (lazy) weights")
+    Ws = [_f32(lin.weight) for lin in lins]
+    if any(W.shape != (H * C, Ws[0].shape[1]) for W in Ws):
+        raise UnsupportedArch("TransformerConv weight shape does not match heads * out_channels")
+    bs = [_f32(lin.bias) if getattr(lin, "bias", None) is not None else None for lin in lins]
+    g_out = g_r = None
+    lin_beta = getattr(conv, "lin_beta", None) if root and getattr(conv, "beta", False) else None
+    if lin_beta is not None:
+        if _lazy(lin_beta):
+            raise UnsupportedArch("TransformerConv with uninitialised (lazy) weights")
+        if tuple(lin_beta.weight.shape) != (1, 3 * H * C) or getattr(lin_beta, "bias", None) is not None:
+            raise UnsupportedArch("TransformerConv lin_beta is not Linear(3 * heads * out_channels, 1, bias=False)")
+        w1, w2, w3 = lin_beta.weight.detach().double().reshape(3, H * C)
+        g_out, g_r = (w1 + w3).to(torch.float32), (w2 - w3).to(torch.float32)
+    term = Term("qkv", rel, Ws[0], heads=H, head_ch=C, bias_l=bs[0], weight_v=Ws[1], bias_v=bs[1],
+                weight_q=Ws[2], bias_q=bs[2], weight_s=Ws[3] if root else None,
+                bias_s=bs[3] if root else None, gate_out=g_out, gate_r=g_r, self_loops=False)
+    return [term], None, None, Ws[0].shape[1], H * C
+
+
 def fold_attention(term):
     """The attention vectors of an "att" term folded through its weights: (v_s, v_d), each
     [heads, f_in], with v_s[h] = W_src[hC:(h+1)C, :]^T att_src[h] (v_d likewise, with W_dst for
@@ -417,7 +474,7 @@ def stack_attention(terms, f_in_pad, f_out_pad):
 
 
 def _check_unmixed(terms):
-    for kind, name in (("att", "GATConv"), ("att2", "GATv2Conv")):
+    for kind, name in (("att", "GATConv"), ("att2", "GATv2Conv"), ("qkv", "TransformerConv")):
         if any(t.kind == kind for t in terms) and not all(t.kind == kind for t in terms):
             raise UnsupportedArch(f"a conv layer mixing {name} with other relations")
 
@@ -555,6 +612,8 @@ def _single_conv_terms(conv, rel, attention=False, bipartite=False):
         return _gat_terms(conv, rel, bipartite)
     if attention and _is_gatv2(conv):
         return _gatv2_terms(conv, rel, bipartite)
+    if attention and _is_transformer(conv):
+        return _transformer_terms(conv, rel, bipartite)
     if name == "GCNConv":
         if getattr(conv, "improved", False) or not getattr(conv, "add_self_loops", True) \
                 or not getattr(conv, "normalize", True):
@@ -609,7 +668,7 @@ def _conv_layer(conv, rel_index, attention=False):
                 raise UnsupportedArch("bipartite relations need the multi-node-type path")
             t, b, wr, fi, fo = _single_conv_terms(sub, rel_index[et], attention)
             if f_out is not None and fo != f_out and \
-                    (t[0].kind in ("att", "att2") or terms[0].kind in ("att", "att2")):
+                    (t[0].kind in ("att", "att2", "qkv") or terms[0].kind in ("att", "att2", "qkv")):
                 raise UnsupportedArch("HeteroConv relations with different output widths")
             terms += t
             if b is not None:
@@ -662,6 +721,8 @@ def _conv_layer_multi(conv, rel_index, node_type_names, attention=False):
             raise UnsupportedArch("GCNConv on a bipartite relation")
         if _is_gatv2(sub):
             raise UnsupportedArch("GATv2Conv on a multi-node-type graph")
+        if _is_transformer(sub):
+            raise UnsupportedArch("TransformerConv on a multi-node-type graph")
         t, b, wr, fi, fo = _single_conv_terms(sub, rel_index[et], attention, s_t != d_t)
         if t[0].kind == "att" and t[0].self_loops:
             raise UnsupportedArch("GATConv(add_self_loops=True) on a multi-node-type graph")
@@ -803,7 +864,8 @@ def compile_arch(arch: nn.Module, edge_type_names=None, node_type_names=None,
     homogenised edge-type order, data.py:743-822) enables HeteroConv relations;
     `node_type_names` with two or more types selects the multi-node-type lowering.
     `attention=True` (opt-in) also lowers GATConv relations, to "att" terms, and GATv2Conv
-    relations, to "att2" terms; by default an arch with either raises UnsupportedArch.
+    relations, to "att2" terms, and TransformerConv relations, to "qkv" terms; by default an arch
+    with any of them raises UnsupportedArch.
     `edge_weight=True`: the arch will be called with an edge_weight.  Only GCNConv and GraphConv take
     one in PyG 2.0.4, so every conv must be one of the two (inside a ConvStack, a BlockStack or a
     PooledModel encoder alike); the program is marked `weighted`.
@@ -942,6 +1004,6 @@ def count_message_passing(arch: nn.Module) -> int:
     for m in arch.modules():
         if any(c.__name__ == "MessagePassing" for c in type(m).__mro__):
             n += 1
-        elif type(m).__name__ in ("GCNConv", "SAGEConv", "GATConv", "GATv2Conv", "GINConv", "GINEConv", "GraphConv") + _RGCN_NAMES:
+        elif type(m).__name__ in ("GCNConv", "SAGEConv", "GATConv", "GATv2Conv", "TransformerConv", "GINConv", "GINEConv", "GraphConv") + _RGCN_NAMES:
             n += 1
     return n

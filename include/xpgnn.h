@@ -40,7 +40,8 @@
  *                                        (v27 addendum, no version change: xpg_layer_desc.pool
  *                                        appended; a conv stack followed by a global mean / add /
  *                                        max readout and a dense head, one output per mask row;
- *                                        XPG_TERM_ATT2 = 7: GATv2Conv layers, enum xpg_term below;
+ *                                        XPG_TERM_ATT2 = 7: GATv2Conv layers, XPG_TERM_QKV = 8:
+ *                                        TransformerConv layers, enum xpg_term below;
  *                                        xpg_masked_forward_w: the same with PyG's edge_weight of
  *                                        GCNConv / GraphConv, struct xpg_edge_weights below;
  *                                        xpg_masked_forward_e: the same with PyG's edge_attr of
@@ -86,7 +87,8 @@ enum xpg_term { XPG_TERM_GCN = 0,   /* D^-1/2 (A_r + I) D^-1/2 over relation r  
                 XPG_TERM_SUM = 4,   /* sum over kept in-edges of relation r (v25; below)      */
                 XPG_TERM_MAX = 5,   /* element-wise max over kept in-edges (v25; below)       */
                 XPG_TERM_REL = 6,   /* every relation's mean / sum, one term (RGCN, v26; below) */
-                XPG_TERM_ATT2 = 7   /* dynamic attention over relation r (GATv2Conv; v27 addendum, below) */ };
+                XPG_TERM_ATT2 = 7,  /* dynamic attention over relation r (GATv2Conv; v27 addendum, below) */
+                XPG_TERM_QKV = 8    /* dot-product attention over relation r (TransformerConv; v27 addendum, below) */ };
 /* ATT2 (v27 addendum: an enum value only; the version, every struct layout and the meaning of
  * every existing plan are unchanged).  One term = one GATv2Conv relation (PyG 2.0.4) and reuses
  * xpg_term_desc's fields: rel, heads, head_ch, neg_slope and self_loops mean what they mean for
@@ -113,6 +115,42 @@ enum xpg_term { XPG_TERM_GCN = 0,   /* D^-1/2 (A_r + I) D^-1/2 over relation r  
  * table (att_dst at layer 1, coef at deeper layers), a non-NULL layer weight (at layer 1: the raw
  * form).  ATT2 plans run on the multi-kernel path only (xpg_forward_describe: `unfused`), launch no
  * degree pass unless another layer needs one, and need no score region. */
+/* QKV (v27 addendum: an enum value only; the version, every struct layout and the meaning of every
+ * existing plan are unchanged).  One term = one TransformerConv relation (PyG 2.0.4) and reuses
+ * xpg_term_desc's fields.  heads and head_ch mean what they mean for ATT; dst_type must be -1 and
+ * the layer's tgt_type NULL; node masks only.  self_loops = 0 and att_dst = NULL are unused.
+ * Edge set of target t in mask row b: every CSR in-edge (u -> t) with bit(b, u) & bit(b, t),
+ * duplicate edges as separate entries, plus the self_mult[r][t] copies of (t -> t) iff bit(b, t);
+ * nothing is added or removed (a masked target has no edges).
+ * n_slices = nb = 3 or 4 names the term's blocks, in the order K = lin_key(x), V = lin_value(x),
+ * Q = lin_query(x) and, with root_weight (nb = 4), S = lin_skip(x), each viewed as
+ * [.][heads][head_ch].  Edge e = (u -> t), head h:
+ *   z_e^h = scale * sum_c Q[t][h][c] * K[u][h][c],
+ *   m = max z, p_e = exp(z_e - m), alpha_e = p_e / (sum p + 1e-16), an empty edge set gives 0,
+ *   out[h * head_ch + c] = sum_e alpha_e^h V[u][h][c].
+ * scale = 1 / sqrt(head_ch), rounded once from fp64, travels in the term's neg_slope field (the
+ * query row is multiplied by it before the products).
+ * The term's epilogue, before the layer's terms are summed: nb = 3: out; nb = 4, att_src NULL:
+ * out + S[t]; nb = 4 with att_src = device [2][f_out_pad] (g_out then g_r, zero-padded; with
+ * lin_beta.weight = [w1 | w2 | w3] over [out, x_r, out - x_r], g_out = w1 + w3 and g_r = w2 - w3):
+ * g = sigmoid(<g_out, out> + <g_r, S[t]>), g * S[t] + (1 - g) * out.  A layer's terms are all QKV
+ * or none and are summed; then the layer's bias (a zero row for TransformerConv, which has no
+ * bias of its own) and act apply; columns past f_out are 0.  The layer is transform-then-aggregate
+ * at every depth, so its `weight` is NULL and no dense launch follows it.
+ * Layer 1: table = device [n0][nb * f_out_pad], per F_0 node the nb blocks, block i =
+ * X[F_0] W_i^T + b_i with padded columns 0; built once per plan (features are never masked).
+ * Layer >= 2: table = device [nb][f_out_pad][f_in_pad], coef = device [nb][f_out_pad] (zeros
+ * without a bias), both zero-padded.  The forward transforms every previous-frontier row of the
+ * call with xpg_dense's kernel into its workspace ([rows * |F_{l-1}|][nb * f_out_pad] per term),
+ * then aggregates.
+ * Refused before any launch (XPG_EINVAL, from xpg_masked_forward, xpg_forward_workspace and
+ * xpg_forward_describe alike, without reading a device pointer): QKV mixed with another kind in a
+ * layer, edge_masks, tgt_type or dst_type != -1, heads <= 0 or heads * head_ch > f_out_pad,
+ * n_slices not 3 or 4, a gate with n_slices == 3, a missing table (coef at deeper layers), a
+ * non-NULL layer weight (at layer 1: the raw form), f_in_pad != the previous layer's f_out_pad.
+ * xpg_masked_forward_w and xpg_masked_forward_e refuse QKV terms as they refuse ATT2.  QKV plans
+ * run on the multi-kernel path only (xpg_forward_describe: `unfused`), launch no degree pass unless
+ * another layer needs one, and need no score region. */
 /* SUM and MAX (v25; node masks only: a plan with edge_masks set and one of them is refused).  The
  * edge set of target t in mask row b for relation r is MEAN's: every CSR in-edge (u -> t) with
  * bit(b, u) & bit(b, t), duplicate edges as separate entries, plus self_mult[r][t] copies of
