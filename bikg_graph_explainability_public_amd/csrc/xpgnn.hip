@@ -9883,6 +9883,41 @@ static int wlm_layout(int64_t n_fits, int64_t rows, int64_t cols, int64_t batch,
   return XPG_OK;
 }
 
+// The fit a layout launches: its family and, for the two templated kernels, the instantiation
+// (single: k_wlm_fit<c, g != 0>, c the smallest CPT that covers cols / 1024 columns per thread;
+// multi: k_wlm_fit_mc<c, g>).  wlm_launch_fit / wlm_fit_grid dispatch on this result and
+// xpg_wlm_describe prints it: the description and the launch share one decision.
+enum WlmFamily { kWlmSingle, kWlmMulti, kWlmGrid3, kWlmGridFused };
+struct WlmVariant {
+  WlmFamily fam;
+  int c, g;
+};
+constexpr int kWlmCpt[] = {1, 2, 4, 8, 16};  // k_wlm_fit<CPT, .> instantiations
+constexpr int kWlmMcArg[] = {1, 2, 4};       // k_wlm_fit_mc<C, G>: both arguments
+
+static WlmVariant wlm_variant(const WlmWs& L, int64_t cols) {
+  if (L.grid) return {L.gf ? kWlmGridFused : kWlmGrid3, 0, 0};
+  if (L.mc) return {kWlmMulti, L.mc_cpl, L.mc_stg};
+  const int64_t cpt = cdiv(cols, 1024);
+  int c = 0;  // 0: more columns per thread than any instantiation holds
+  for (const int v : kWlmCpt)
+    if (!c && cpt <= v) c = v;
+  return {kWlmSingle, c, L.stage ? 1 : 0};
+}
+
+static std::string wlm_variant_name(const WlmVariant& V) {
+  switch (V.fam) {
+    case kWlmSingle:
+      return "single<CPT=" + std::to_string(V.c) + (V.g ? ",stage>" : ",nostage>");
+    case kWlmMulti:
+      return "multi<C=" + std::to_string(V.c) + ",G=" + std::to_string(V.g) + ">";
+    case kWlmGrid3:
+      return "grid3";
+    default:
+      return "grid_fused";
+  }
+}
+
 static int wlm_fit_grid(int64_t n_fits, const uint32_t* bits, int64_t rows, int64_t cols, int64_t batch,
                         const float* y, const double* kernel, const xpg_wlm_params& P, int64_t step0, float* w,
                         float* adam_m, float* adam_v, double* losses, int32_t* best_epoch, int32_t* status, char* ws,
@@ -9897,7 +9932,7 @@ static int wlm_fit_grid(int64_t n_fits, const uint32_t* bits, int64_t rows, int6
   float* p_hist = reinterpret_cast<float*>(ws + L.phist_off);
   double* tk_part = reinterpret_cast<double*>(ws + L.tk_off);
   double* aw_part = reinterpret_cast<double*>(ws + L.aw_off);
-  if (L.gf) {
+  if (wlm_variant(L, cols).fam == kWlmGridFused) {
     uint64_t* gx = reinterpret_cast<uint64_t*>(ws + L.gfx_off);
     uint32_t* err = reinterpret_cast<uint32_t*>(ws + L.gferr_off);
     const int64_t n_gx = (int64_t)batch * (L.gf_nwg + 1);
@@ -9983,6 +10018,49 @@ int xpg_wlm_plan(int64_t n_fits, int64_t rows, int64_t cols, int64_t batch, int3
   if (rc) return rc;
   *kind = L.grid ? (L.gf ? XPG_WLM_GRID_FUSED : XPG_WLM_GRID) : (L.mc ? XPG_WLM_MULTI : XPG_WLM_SINGLE);
   *parts = L.grid ? (L.gf ? L.gf_nwg : 1) : (L.mc ? L.P : 1);
+  return XPG_OK;
+}
+
+int xpg_wlm_describe(int64_t n_fits, int64_t rows, int64_t cols, int64_t batch, char* buf, size_t n) {
+  XPG_REQ(buf != nullptr && n > 0, "wlm_describe: no buffer");
+  buf[0] = 0;
+  WlmWs L;
+  int rc = wlm_layout(n_fits, rows, cols, batch, &L);
+  if (rc) return rc;
+  const WlmVariant V = wlm_variant(L, cols);
+  XPG_REQ(V.fam != kWlmSingle || V.c > 0, "wlm_fit: unsupported column count");
+  std::string s = wlm_variant_name(V);
+  switch (V.fam) {
+    case kWlmSingle:
+      s += " n_bs=" + std::to_string(L.n_bs) + " n_ds=" + std::to_string(L.n_ds);
+      break;
+    case kWlmMulti:
+      s += " P=" + std::to_string(L.P) + " wpp=" + std::to_string(L.wpp) + " ds=" + std::to_string(L.mc_ds);
+      break;
+    case kWlmGrid3:
+      s += " n_wg=" + std::to_string(L.n_wg);
+      break;
+    case kWlmGridFused:
+      s += " ch=" + std::to_string(L.gf_ch) + " nwg=" + std::to_string(L.gf_nwg) + " nrbp=" +
+           std::to_string(L.gf_nrbp);
+      break;
+  }
+  if (s.size() + 1 > n) return fail(XPG_ENOSPC, "wlm_describe: buffer too small");
+  std::memcpy(buf, s.c_str(), s.size() + 1);
+  return XPG_OK;
+}
+
+int xpg_wlm_variants(char* buf, size_t n) {
+  XPG_REQ(buf != nullptr && n > 0, "wlm_variants: no buffer");
+  buf[0] = 0;
+  std::string s;
+  for (const int g : {1, 0})
+    for (const int c : kWlmCpt) s += wlm_variant_name({kWlmSingle, c, g}) + "\n";
+  for (const int c : kWlmMcArg)
+    for (const int g : kWlmMcArg) s += wlm_variant_name({kWlmMulti, c, g}) + "\n";
+  s += wlm_variant_name({kWlmGrid3, 0, 0}) + "\n" + wlm_variant_name({kWlmGridFused, 0, 0}) + "\n";
+  if (s.size() + 1 > n) return fail(XPG_ENOSPC, "wlm_variants: buffer too small");
+  std::memcpy(buf, s.c_str(), s.size() + 1);
   return XPG_OK;
 }
 
@@ -10150,11 +10228,12 @@ static int wlm_launch_fit(int64_t n_fits, const uint32_t* bits, int64_t rows, in
   const int words = words_of(cols);
   const int ic = static_cast<int>(cols), ib = static_cast<int>(batch);
   const unsigned nf = static_cast<unsigned>(n_fits);
+  const WlmVariant V = wlm_variant(L, cols);  // the kernel this launch takes (xpg_wlm_describe's)
   bool launched = (which & 1) == 0;
   // the multi-workgroup exchange's error word (nonzero: a partner's poll timed out, the weights
   // are invalid) reaches the caller's status through k_wlm_loss_best
   const uint32_t* errw = L.mc ? reinterpret_cast<uint32_t*>(ws + L.cnt_off) + n_fits : nullptr;
-  if (L.mc && (which & 1)) {
+  if (V.fam == kWlmMulti && (which & 1)) {
     uint32_t* cnt = reinterpret_cast<uint32_t*>(ws + L.cnt_off);
     uint64_t* xp = reinterpret_cast<uint64_t*>(ws + L.xp_off);
     // granule tags carry a per-call epoch (stale cache lines of earlier calls never match)
@@ -10171,7 +10250,7 @@ static int wlm_launch_fit(int64_t n_fits, const uint32_t* bits, int64_t rows, in
     const int fault = fault_env > 0 ? fault_env : -1;
     const dim3 grid(static_cast<unsigned>(L.xcd ? 8 * L.P * cdiv(n_fits, 8) : n_fits * L.P));
 #define XPG_WLM_MC(C, G)                                                                                    \
-    if (!launched && L.mc_cpl == C && L.mc_stg == G) {                                                      \
+    if (!launched && V.c == C && V.g == G) {                                                                \
       XPG_HIP(lds_limit(reinterpret_cast<const void*>(&k_wlm_fit_mc<C, G>))); \
       hipLaunchKernelGGL((k_wlm_fit_mc<C, G>), grid, dim3(1024), L.lds_mc, st, bits, colbits, rows, ic, words, ib, \
                          L.bw, L.P, L.wpp, L.mc_ds, n_fits, L.xcd ? 1 : 0, kernel, stp, *params, w, adam_m,      \
@@ -10186,9 +10265,8 @@ static int wlm_launch_fit(int64_t n_fits, const uint32_t* bits, int64_t rows, in
 #undef XPG_WLM_MC
     if (!launched) return fail(XPG_EINVAL, "wlm_fit: unsupported slice width");
   }
-  const int cpt = static_cast<int>(cdiv(cols, 1024));
 #define XPG_WLM(C, TL)                                                                                     \
-  if (!launched && cpt <= C && L.stage == TL) {                                                                      \
+  if (!launched && V.fam == kWlmSingle && V.c == C && (V.g != 0) == TL) {                                  \
     XPG_HIP(lds_limit(reinterpret_cast<const void*>(&k_wlm_fit<C, TL>)));     \
     hipLaunchKernelGGL((k_wlm_fit<C, TL>), dim3(nf), dim3(1024), L.lds, st, bits, colbits, rows, ic, words, \
                        ib, L.bw, L.n_bs, L.n_ds, kernel, stp, *params, w, adam_m, adam_v, p_hist, w_hist,  \

@@ -1758,6 +1758,32 @@ def wlm_plan(n_fits, rows, cols, batch):
     return WLM_KINDS[kind.value], parts.value
 
 
+# every variant name wlm_describe can report (the library's own list: xpg_wlm_variants, checked
+# against this tuple by tests/test_fit_cpu.py): k_wlm_fit<CPT, STAGE>, k_wlm_fit_mc<C, G>, the
+# three-launch grid fit and k_gw_fused
+WLM_VARIANTS = tuple(
+    [f"single<CPT={c},{s}>" for s in ("stage", "nostage") for c in (1, 2, 4, 8, 16)] +
+    [f"multi<C={c},G={g}>" for c in (1, 2, 4) for g in (1, 2, 4)] + ["grid3", "grid_fused"])
+
+
+def wlm_describe(n_fits, rows, cols, batch):
+    """The fit kernel wlm_fit launches for a shape on the current device under the current
+    XPG_WLM setting, as text (xpg_wlm_describe): the variant (one of WLM_VARIANTS) and the
+    planner's split, e.g. "single<CPT=2,stage> n_bs=3 n_ds=1", "multi<C=1,G=1> P=13 wpp=3 ds=1",
+    "grid3 n_wg=9", "grid_fused ch=1 nwg=9 nrbp=8".  A host query of the launcher's own decision
+    (nothing is launched)."""
+    buf = ctypes.create_string_buffer(256)
+    _lib.check(_lib.load().xpg_wlm_describe(int(n_fits), int(rows), int(cols), int(batch), buf, len(buf)))
+    return buf.value.decode()
+
+
+def wlm_variants():
+    """The library's list of variant names (xpg_wlm_variants); equals WLM_VARIANTS."""
+    buf = ctypes.create_string_buffer(2048)
+    _lib.check(_lib.load().xpg_wlm_variants(buf, len(buf)))
+    return tuple(buf.value.decode().split())
+
+
 class PreparedFit:
     """A fresh surrogate fit (`wlm_fit` from w0) split in its two launches on static buffers of
     one shape (xpg_wlm_prepare / xpg_wlm_fit_prepared, ABI v12): `prepare` runs the prologue

@@ -53,6 +53,9 @@
  *   xpg_sampler_describe               — none: host query of the device samplers' own dispatch (which
  *                                        k_shapley / k_shapley_flat / k_communities instantiation
  *                                        a shape launches, and its grid), for tests and logs
+ *   xpg_wlm_describe / xpg_wlm_variants — none: host queries of xpg_wlm_fit's own dispatch (which
+ *                                        k_wlm_fit / k_wlm_fit_mc instantiation or grid fit a
+ *                                        shape launches, and the planner's split), for tests and logs
  *   xpg_dense                          — the dense feature x weight contraction inside each layer
  *                                        (PyG Linear / GCNConv.lin / SAGEConv.lin_l|lin_r)
  *   xpg_wlm_fit                        — train_model's epoch loop     wlm.py:132-278 with
@@ -69,7 +72,7 @@
 extern "C" {
 #endif
 
-#define XPG_ABI_VERSION 27
+#define XPG_ABI_VERSION 28
 #define XPG_MAX_TERMS 8
 
 typedef void* xpg_stream_t; /* hipStream_t */
@@ -744,6 +747,22 @@ int xpg_wlm_workspace(int64_t n_fits, int64_t rows, int64_t cols, int64_t batch,
 enum xpg_wlm_kind { XPG_WLM_SINGLE = 0, XPG_WLM_MULTI = 1, XPG_WLM_GRID = 2, XPG_WLM_GRID_FUSED = 3 };
 int xpg_wlm_plan(int64_t n_fits, int64_t rows, int64_t cols, int64_t batch, int32_t* kind,
                  int32_t* parts);
+/* The fit kernel xpg_wlm_fit / xpg_wlm_fit_from launch for a shape on the current device under
+ * the current XPG_WLM setting, as text (v28): the variant and the planner's split, one of
+ *   `single<CPT=2,stage> n_bs=3 n_ds=1`   k_wlm_fit<CPT, STAGE> (`stage` / `nostage`), batch and
+ *                                         column slices per wave item
+ *   `multi<C=1,G=1> P=13 wpp=3 ds=1`      k_wlm_fit_mc<C, G>, parts per fit, mask words per part,
+ *                                         column-row slices per lane
+ *   `grid3 n_wg=9`                        the three-launch grid fit, column chunks
+ *   `grid_fused ch=1 nwg=9 nrbp=8`        k_gw_fused: chunks per workgroup, workgroups, padded
+ *                                         32-row blocks
+ * A HOST function: it launches nothing.  The launch dispatches on the same variant record this
+ * text is printed from.  Fails where the fit's layout fails; XPG_ENOSPC when `n` bytes do not
+ * hold the text and its terminator. */
+int xpg_wlm_describe(int64_t n_fits, int64_t rows, int64_t cols, int64_t batch, char* buf, size_t n);
+/* Every variant name (the text before the first space) xpg_wlm_describe can write, one per line
+ * (v28): ten `single<...>`, nine `multi<...>`, `grid3`, `grid_fused`. */
+int xpg_wlm_variants(char* buf, size_t n);
 /* Runs ceil(rows / batch) Adam steps of train_model over consecutive row batches for n_fits
  * independent surrogates (e.g. the `times` repeats of Explainer.run), one workgroup each.
  * Arrays are fit-major and contiguous: bits [n_fits][rows][words], y / kernel [n_fits][rows],

@@ -377,7 +377,7 @@ def test_abi_is_additive():
     for name in ("xpg_forward_workspace_post", "xpg_masked_forward_post", "xpg_forward_describe_post",
                  "xpg_post_rows", "xpg_post_describe"):
         assert name in _lib.EXPORTED and hasattr(lib, name)
-    assert _lib.ABI_VERSION == 27 and lib.xpg_abi_version() == 27
+    assert _lib.ABI_VERSION == 28 and lib.xpg_abi_version() == 28
     assert [f[0] for f in _lib.LayerDesc._fields_[-2:]] == ["seg_rel", "pool"]
     assert _lib.ForwardPlanDesc._fields_[-1][0] == "dot_scale"
     assert [f[0] for f in _lib.PostDesc._fields_] == ["norm", "eps", "scale", "shift", "gamma", "beta",

@@ -219,7 +219,7 @@ PLANS = [
 
 
 def test_abi_is_additive():
-    assert _lib.ABI_VERSION == 27 and _lib.ForwardPlanDesc._fields_[-1][0] == "dot_scale"
+    assert _lib.ABI_VERSION == 28 and _lib.ForwardPlanDesc._fields_[-1][0] == "dot_scale"
     assert [f[0] for f in _lib.ClassOut._fields_] == ["kind", "col"] and ctypes.sizeof(_lib.ClassOut) == 8
     assert _lib.CLASS_KIND == {None: 0, "softmax": 1, "log_softmax": 2}
     assert {"xpg_forward_workspace_c", "xpg_masked_forward_c", "xpg_forward_describe_c",

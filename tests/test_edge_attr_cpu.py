@@ -301,7 +301,7 @@ def test_abi_is_additive():
     for name in ("xpg_forward_workspace_e", "xpg_masked_forward_e", "xpg_forward_describe_e",
                  "xpg_forward_workspace_w", "xpg_masked_forward_w", "xpg_forward_describe_w"):
         assert name in _lib.EXPORTED and hasattr(lib, name)
-    assert _lib.ABI_VERSION == 27 and lib.xpg_abi_version() == 27
+    assert _lib.ABI_VERSION == 28 and lib.xpg_abi_version() == 28
     assert ctypes.sizeof(_lib.LayerEfeat) == 24 and ctypes.sizeof(_lib.EdgeFeats) == 8
     assert ctypes.sizeof(_lib.LayerWeights) == 32 and ctypes.sizeof(_lib.EdgeWeights) == 24
     assert ctypes.sizeof(_lib.PostDesc) == 48

@@ -202,7 +202,7 @@ def test_abi_is_additive():
     lib = _lib.load()
     for name in ("xpg_forward_workspace_w", "xpg_masked_forward_w", "xpg_forward_describe_w"):
         assert name in _lib.EXPORTED and hasattr(lib, name)
-    assert _lib.ABI_VERSION == 27 and lib.xpg_abi_version() == 27
+    assert _lib.ABI_VERSION == 28 and lib.xpg_abi_version() == 28
     assert ctypes.sizeof(_lib.LayerWeights) == 32 and ctypes.sizeof(_lib.EdgeWeights) == 24
     assert ctypes.sizeof(_lib.PostDesc) == 48
     assert [f[0] for f in _lib.LayerDesc._fields_[-2:]] == ["seg_rel", "pool"]

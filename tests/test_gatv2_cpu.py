@@ -214,7 +214,7 @@ def _refused(desc, msg):
 
 
 def test_abi_is_unchanged():
-    assert _lib.TERM["att2"] == 7 and _lib.ABI_VERSION == 27
+    assert _lib.TERM["att2"] == 7 and _lib.ABI_VERSION == 28
     assert [f[0] for f in _lib.LayerDesc._fields_][-2:] == ["seg_rel", "pool"]
     assert _lib.ForwardPlanDesc._fields_[-1][0] == "dot_scale"
     assert {k: v for k, v in _lib.TERM.items() if k != "att2"} == \

@@ -163,7 +163,7 @@ def _ws(desc, rows=70):
 def test_layer_desc_matches_header():
     """`pool` is appended after seg_rel, the plan struct and the version are unchanged."""
     assert [f[0] for f in _lib.LayerDesc._fields_][-2:] == ["seg_rel", "pool"]
-    assert _lib.ForwardPlanDesc._fields_[-1][0] == "dot_scale" and _lib.ABI_VERSION == 27
+    assert _lib.ForwardPlanDesc._fields_[-1][0] == "dot_scale" and _lib.ABI_VERSION == 28
     assert _lib.POOL == {None: 0, "mean": 1, "sum": 2, "max": 3}
     assert {"xpg_pool_workspace", "xpg_pool_rows", "xpg_pool_describe"} <= set(_lib.EXPORTED)
 

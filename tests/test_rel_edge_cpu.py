@@ -340,7 +340,7 @@ def forward_rc(desc, rows=70):
 
 
 def test_abi_v27():
-    assert _lib.ABI_VERSION == 27 and _lib.load().xpg_abi_version() == 27
+    assert _lib.ABI_VERSION == 28 and _lib.load().xpg_abi_version() == 28
     assert _lib.ForwardPlanDesc._fields_[-1][0] == "dot_scale"
     assert _lib.ForwardPlanDesc.dot_scale.offset == _lib.ForwardPlanDesc.dot_act.offset + 8 \
         or _lib.ForwardPlanDesc.dot_scale.offset == _lib.ForwardPlanDesc.dot_act.offset + 4

@@ -260,7 +260,7 @@ def _refused(desc, msg):
 
 
 def test_abi_is_unchanged():
-    assert _lib.TERM_QKV == 8 and _lib.ABI_VERSION == 27
+    assert _lib.TERM_QKV == 8 and _lib.ABI_VERSION == 28
     assert _lib.TERM == {"gcn": 0, "mean": 1, "root": 2, "att": 3, "sum": 4, "max": 5, "rel": 6, "att2": 7}
     assert [f[0] for f in _lib.LayerDesc._fields_][-2:] == ["seg_rel", "pool"]
     assert _lib.ForwardPlanDesc._fields_[-1][0] == "dot_scale"
