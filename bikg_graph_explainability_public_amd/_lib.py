@@ -170,6 +170,12 @@ _SIGS = {
     "xpg_forward_describe_c": ([ctypes.POINTER(ForwardPlanDesc), ctypes.POINTER(PostDesc),
                                 ctypes.POINTER(EdgeWeights), ctypes.POINTER(EdgeFeats), ctypes.POINTER(ClassOut),
                                 c_i64, ctypes.c_char_p, ctypes.c_size_t], c_i32),
+    "xpg_forward_kernels": ([ctypes.POINTER(ForwardPlanDesc), c_i64, ctypes.c_char_p,
+                             ctypes.c_size_t], c_i32),
+    "xpg_forward_kernels_c": ([ctypes.POINTER(ForwardPlanDesc), ctypes.POINTER(PostDesc),
+                               ctypes.POINTER(EdgeWeights), ctypes.POINTER(EdgeFeats), ctypes.POINTER(ClassOut),
+                               c_i64, ctypes.c_char_p, ctypes.c_size_t], c_i32),
+    "xpg_forward_variants": ([ctypes.c_char_p, ctypes.c_size_t], c_i32),
     "xpg_class_out_rows": ([c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_vp], c_i32),
     "xpg_post_rows": ([c_vp, c_i64, c_i64, c_i64, ctypes.POINTER(PostDesc), c_vp, c_i64, c_i64, c_i64,
                        c_vp, c_vp], c_i32),

@@ -7535,77 +7535,136 @@ struct OutColumn {
   float* y = nullptr;
 };
 
+// The dense and aggregation kernels by the name xpg_forward_kernels reports.  dense_pick / agg_pick
+// are the one selection each (host only: shape, term kinds and the environment), shared by the
+// launch and by the query, so a test that asserts the reported name asserts the kernel that ran;
+// xpg_forward_variants lists these tables, so no kernel runs that it does not list.
+typedef void (*DenseFn)(const float*, int64_t, int64_t, const float*, int64_t, int, const float*, int, int, float*,
+                        int64_t, const int32_t*, int64_t, int, int, const float*, const float*, int, float*);
+struct DenseVariant {
+  DenseFn fn;
+  const char* name;
+  int nt;
+  bool head;
+};
+#define XPG_DV(NT) {k_dense<NT, false>, "k_dense<" #NT ",0>", NT, false}, {k_dense<NT, true>, "k_dense<" #NT ",1>", NT, true}
+const DenseVariant kDenseVariants[] = {XPG_DV(1), XPG_DV(2), XPG_DV(3), XPG_DV(4),
+                                       XPG_DV(5), XPG_DV(6), XPG_DV(7), XPG_DV(8)};
+#undef XPG_DV
+struct DensePick {
+  const DenseVariant* v;
+  int groups;  // column groups (waves per 32-row block): 1, or 4 when n_pad is 128 or 256
+};
+int dense_pick(int64_t k_pad, int64_t n_pad, bool head, DensePick* s) {
+  XPG_REQ(k_pad % 8 == 0 && n_pad % 32 == 0 && n_pad >= 32 && n_pad <= 256,
+          "xpg_dense: k_pad % 8, n_pad in {32..256} step 32 required");
+  // 4+ column tiles: split them over column groups of one or two tiles per wave (a 128-wide layer
+  // on one wave per 32 rows left a workgroup of 4 waves per CU, latency-bound)
+  const int tiles = static_cast<int>(n_pad / 32);
+  s->groups = tiles >= 4 && tiles % 4 == 0 ? 4 : 1;
+  s->v = nullptr;
+  for (const DenseVariant& v : kDenseVariants)
+    if (v.nt == tiles / s->groups && v.head == head) s->v = &v;
+  if (!s->v) return fail(XPG_EINVAL, "xpg_dense: unsupported n_pad");
+  return XPG_OK;
+}
+
 int launch_dense(const float* A, int64_t M, int64_t lda, const float* W, int64_t ldw, int64_t k_pad,
                  const float* bias, int64_t n_real, int64_t n_pad, int act, float* C, int64_t ldc,
                  hipStream_t st, const int32_t* row_type = nullptr, int64_t type_mod = 1, int bias_ld = 0,
                  const OutColumn* head = nullptr) {
-  XPG_REQ(k_pad % 8 == 0 && n_pad % 32 == 0 && n_pad >= 32 && n_pad <= 256,
-          "xpg_dense: k_pad % 8, n_pad in {32..256} step 32 required");
+  DensePick pick;
+  if (const int rc = dense_pick(k_pad, n_pad, head != nullptr, &pick)) return rc;
   XPG_REQ(lda % 4 == 0 && ldw % 4 == 0, "xpg_dense: lda/ldw must be multiples of 4");
   if (M <= 0) return XPG_OK;
-  // 4+ column tiles: split them over column groups of one or two tiles per wave (a 128-wide layer
-  // on one wave per 32 rows left a workgroup of 4 waves per CU, latency-bound)
-  const int tiles = static_cast<int>(n_pad / 32);
-  const int groups = tiles >= 4 && tiles % 4 == 0 ? 4 : 1;
+  const int groups = pick.groups;
   const int64_t waves = cdiv(M, 32) * groups;
   dim3 grid(static_cast<unsigned>(cdiv(waves, 4))), block(256);
   const int kp = static_cast<int>(k_pad), nr = static_cast<int>(n_real);
-  switch (tiles / groups) {
-#define XPG_DENSE_CASE(NT)                                                                                      \
-    case NT:                                                                                                    \
-      if (head)                                                                                                 \
-        hipLaunchKernelGGL((k_dense<NT, true>), grid, block, 0, st, A, M, lda, W, ldw, kp, bias, nr, act, C,   \
-                           ldc, row_type, type_mod, bias_ld, groups, head->w, head->b, head->act, head->y);     \
-      else                                                                                                      \
-        hipLaunchKernelGGL((k_dense<NT, false>), grid, block, 0, st, A, M, lda, W, ldw, kp, bias, nr, act, C,  \
-                           ldc, row_type, type_mod, bias_ld, groups, nullptr, nullptr, 0, nullptr);             \
-      break;
-    XPG_DENSE_CASE(1) XPG_DENSE_CASE(2) XPG_DENSE_CASE(3) XPG_DENSE_CASE(4)
-    XPG_DENSE_CASE(5) XPG_DENSE_CASE(6) XPG_DENSE_CASE(7) XPG_DENSE_CASE(8)
-#undef XPG_DENSE_CASE
-    default: return fail(XPG_EINVAL, "xpg_dense: unsupported n_pad");
-  }
+  if (head)
+    hipLaunchKernelGGL(pick.v->fn, grid, block, 0, st, A, M, lda, W, ldw, kp, bias, nr, act, C, ldc, row_type,
+                       type_mod, bias_ld, groups, head->w, head->b, head->act, head->y);
+  else
+    hipLaunchKernelGGL(pick.v->fn, grid, block, 0, st, A, M, lda, W, ldw, kp, bias, nr, act, C, ldc, row_type,
+                       type_mod, bias_ld, groups, static_cast<const float*>(nullptr),
+                       static_cast<const float*>(nullptr), 0, static_cast<float*>(nullptr));
   XPG_LAUNCHED();
+  return XPG_OK;
+}
+
+typedef void (*AggFn)(AggArgs);
+struct AggVariant {
+  AggFn fn;
+  const char* name;
+  int rows;  // 1: k_agg_l1_rows<x, y> (x = features per wave, y = ONE); 0: k_agg<l1, x, y> (x = LPS, y = NV)
+  int l1, x, y;
+};
+#define XPG_AV_ROWS(W, ONE) {k_agg_l1_rows<W, ONE != 0>, "k_agg_l1_rows<" #W "," #ONE ">", 1, 1, W, ONE}
+#define XPG_AV(L1, LPS, NV) {k_agg<L1 != 0, LPS, NV>, "k_agg<" #L1 "," #LPS "," #NV ">", 0, L1, LPS, NV}
+#define XPG_AV_ALL(L1)                                                                                        \
+  XPG_AV(L1, 8, 1), XPG_AV(L1, 16, 1), XPG_AV(L1, 24, 1), XPG_AV(L1, 32, 1), XPG_AV(L1, 40, 1), XPG_AV(L1, 48, 1), \
+      XPG_AV(L1, 56, 1), XPG_AV(L1, 64, 1), XPG_AV(L1, 64, 2), XPG_AV(L1, 64, 4)
+const AggVariant kAggVariants[] = {XPG_AV_ROWS(32, 0), XPG_AV_ROWS(32, 1), XPG_AV_ROWS(64, 0), XPG_AV_ROWS(64, 1),
+                                   XPG_AV_ALL(0), XPG_AV_ALL(1)};
+#undef XPG_AV_ALL
+#undef XPG_AV
+#undef XPG_AV_ROWS
+struct AggPick {
+  const AggVariant* v;
+  int slices;  // k_agg_l1_rows: feature slices (waves) per 64 mask rows of a target; k_agg: 1
+  int lps;     // k_agg: lanes per (mask row, target)
+};
+// `l1`: the table form of layer 1; `edge_masks`: the layer carries edge columns (agg_eid)
+int agg_pick(bool l1, bool edge_masks, int width, const int* kind, int n_terms, AggPick* s) {
+  XPG_REQ(width % 32 == 0 && width > 0, "agg: row width must be a positive multiple of 32");
+  // layer 1, widths 32 / 64 / 128 / 256, no edge masks: lanes = mask rows (XPG_AGG_GENERIC=1, a diagnostics
+  // switch: the generic k_agg, which the parity suite compares bitwise)
+  int generic = 0;
+  if (const int rc = diag_env("XPG_AGG_GENERIC", &generic)) return rc;
+  s->v = nullptr;
+  if (l1 && !edge_masks && (width == 32 || width == 64 || width == 128 || width == 256) && !generic) {
+    const int slice = width == 32 ? 32 : 64;  // features per wave
+    bool one = kind[0] != XPG_TERM_ROOT;
+    for (int k = 1; k < n_terms; ++k) one = one && kind[k] == XPG_TERM_ROOT;
+    s->slices = width / slice;
+    s->lps = 0;
+    for (const AggVariant& v : kAggVariants)
+      if (v.rows && v.x == slice && v.y == (one ? 1 : 0)) s->v = &v;
+    return XPG_OK;
+  }
+  const int f4 = width / 4;  // float4 chunks per row (>= 8)
+  const int lps = f4 >= 64 ? 64 : f4;
+  const int nv = f4 / lps;
+  XPG_REQ(f4 % lps == 0 && (nv == 1 || nv == 2 || nv == 4), "agg: unsupported row width");
+  s->slices = 1;
+  s->lps = lps;
+  // widths that are odd multiples of 32 below 256 (e.g. 96) map to lps = f4 (non power of 2)
+  for (const AggVariant& v : kAggVariants)
+    if (!v.rows && v.l1 == (l1 ? 1 : 0) && v.x == lps && v.y == nv) s->v = &v;
+  if (!s->v) return fail(XPG_EINVAL, "agg: unsupported row width " + std::to_string(width));
   return XPG_OK;
 }
 
 template <bool L1>
 int launch_agg(const AggArgs& a, hipStream_t st) {
-  XPG_REQ(a.width % 32 == 0 && a.width > 0, "agg: row width must be a positive multiple of 32");
-  // layer 1, widths 32 / 64 / 128 / 256, no edge masks: lanes = mask rows (XPG_AGG_GENERIC=1, a diagnostics
-  // switch: the generic k_agg, which the parity suite compares bitwise)
-  int generic = 0;
-  if (const int rc = diag_env("XPG_AGG_GENERIC", &generic)) return rc;
-  if (L1 && !a.agg_eid && (a.width == 32 || a.width == 64 || a.width == 128 || a.width == 256) && !generic) {
-    const int slice = a.width == 32 ? 32 : 64;  // features per wave
-    const int64_t waves = cdiv(a.rows, 64) * a.n_tgt * (a.width / slice);
+  AggPick pick;
+  if (const int rc = agg_pick(L1, a.agg_eid != nullptr, a.width, a.kind, a.n_terms, &pick)) return rc;
+  if (pick.v->rows) {
+    const int64_t waves = cdiv(a.rows, 64) * a.n_tgt * pick.slices;
     if (waves == 0) return XPG_OK;
     const dim3 grid(static_cast<unsigned>(cdiv(waves, 4))), block(256);
     AggArgs b = a;
     if (const int rc = diag_env("XPG_L1_DBG", &b.rows_blk)) return rc;
-    bool one = a.kind[0] != XPG_TERM_ROOT;
-    for (int k = 1; k < a.n_terms; ++k) one = one && a.kind[k] == XPG_TERM_ROOT;
-    if (slice == 64 && one) hipLaunchKernelGGL((k_agg_l1_rows<64, true>), grid, block, 0, st, b);
-    else if (slice == 64) hipLaunchKernelGGL((k_agg_l1_rows<64, false>), grid, block, 0, st, b);
-    else if (one) hipLaunchKernelGGL((k_agg_l1_rows<32, true>), grid, block, 0, st, b);
-    else hipLaunchKernelGGL((k_agg_l1_rows<32, false>), grid, block, 0, st, b);
+    hipLaunchKernelGGL(pick.v->fn, grid, block, 0, st, b);
     XPG_LAUNCHED();
     return XPG_OK;
   }
-  const int f4 = a.width / 4;  // float4 chunks per row (>= 8)
-  const int lps = f4 >= 64 ? 64 : f4;
-  const int nv = f4 / lps;
-  XPG_REQ(f4 % lps == 0 && (nv == 1 || nv == 2 || nv == 4), "agg: unsupported row width");
-  const int64_t threads = a.rows * a.n_tgt * lps;
+  const int64_t threads = a.rows * a.n_tgt * pick.lps;
   if (threads == 0) return XPG_OK;
   dim3 grid(static_cast<unsigned>(cdiv(threads, 256))), block(256);
-#define XPG_AGG(LPS, NV) \
-  if (lps == LPS && nv == NV) { hipLaunchKernelGGL((k_agg<L1, LPS, NV>), grid, block, 0, st, a); XPG_LAUNCHED(); return XPG_OK; }
-  XPG_AGG(8, 1) XPG_AGG(16, 1) XPG_AGG(32, 1) XPG_AGG(64, 1) XPG_AGG(64, 2) XPG_AGG(64, 4)
-  // widths that are odd multiples of 32 below 256 (e.g. 96) map to lps = f4 (non power of 2)
-  XPG_AGG(24, 1) XPG_AGG(40, 1) XPG_AGG(48, 1) XPG_AGG(56, 1)
-#undef XPG_AGG
-  return fail(XPG_EINVAL, "agg: unsupported row width " + std::to_string(a.width));
+  hipLaunchKernelGGL(pick.v->fn, grid, block, 0, st, a);
+  XPG_LAUNCHED();
+  return XPG_OK;
 }
 
 // k_agg_w for one layer of a weighted plan: launch_agg's generic lane mapping (no rows-as-lanes
@@ -7983,10 +8042,26 @@ bool forward_is(const char* v) {
   return v ? env && std::strcmp(env, v) == 0 : env && *env;
 }
 
-// Fused single-launch forward when the plan fits (returns 1 when it does not apply).  `dry`: the
-// decision only (XPG_OK = the kernel takes the plan), nothing launched, no device touched.
-int try_fused_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t rows, float* y, hipStream_t st,
-                      bool dry = false) {
+// The fused and rows kernels by the name xpg_forward_kernels reports (fused_pick / rows_pick: the
+// one selection each, shared by the launch and by the query; host only).
+struct FusedVariant {
+  void (*fn)(const FusedArgs);
+  const char* name;
+  int wpb;
+};
+const FusedVariant kFusedVariants[] = {{k_fused_forward<8>, "k_fused_forward<8>", 8},
+                                       {k_fused_forward<4>, "k_fused_forward<4>", 4},
+                                       {k_fused_forward<2>, "k_fused_forward<2>", 2}};
+struct FusedPick {
+  const FusedVariant* v;
+  size_t lds;
+  FusedArgs a;  // everything but bits and y
+};
+
+// The fused kernel's variant, LDS size and arguments when the plan fits (returns 1 when it does
+// not apply): plan fields and the environment only, no device touched.
+int fused_pick(const xpg_forward_plan* p, int64_t rows, FusedPick* s) {
+  FusedArgs& a = s->a;
   // opt-in (XPG_FORWARD=fused): per-row latency chains make it slower than k_rows_forward
   if (!forward_is("fused")) return 1;
   if (plan_has_attention(p)) return 1;  // attention: multi-kernel path only
@@ -7995,11 +8070,8 @@ int try_fused_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t r
   if (plan_pool(p)) return 1;           // pooled plans (readout): multi-kernel path only
   if (p->n_layers > kFusedMaxLayers || p->n_head > kFusedMaxHead || plan_multi_type(p)) return 1;
   if (p->edge_masks || p->edge_dot) return 1;  // edge problems: multi-kernel path only
-  FusedArgs a;
   std::memset(&a, 0, sizeof(a));
   a.rows = rows;
-  a.bits = bits;
-  a.y = y;
   a.words = words_of(p->cols);
   a.n0 = p->n0;
   a.n_rel = p->n_rel;
@@ -8074,28 +8146,34 @@ int try_fused_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t r
   a.o_a = a.o_h1 + static_cast<int>(up4(h_max));
   a.wave_floats = a.o_a + static_cast<int>(up4(a_max));
   const int64_t lds_cap = 160 * 1024 / 4 - 64;
-  int wpb = 0;
-  for (int c : {8, 4, 2}) {
-    if (shared + (int64_t)c * a.wave_floats <= lds_cap) {
-      wpb = c;
+  s->v = nullptr;
+  for (const FusedVariant& v : kFusedVariants) {  // the most waves per block whose scratch fits
+    if (shared + (int64_t)v.wpb * a.wave_floats <= lds_cap) {
+      s->v = &v;
       break;
     }
   }
-  if (!wpb) return 1;
+  if (!s->v) return 1;
+  s->lds = sizeof(float) * (size_t)(shared + (int64_t)s->v->wpb * a.wave_floats);
+  return XPG_OK;
+}
+
+// Fused single-launch forward when the plan fits (returns 1 when it does not apply).  `dry`: the
+// decision only (XPG_OK = the kernel takes the plan), nothing launched, no device touched.
+int try_fused_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t rows, float* y, hipStream_t st,
+                      bool dry = false) {
+  FusedPick pick;
+  if (const int rc = fused_pick(p, rows, &pick)) return rc;
   if (dry) return XPG_OK;
-  const size_t lds = sizeof(float) * (size_t)(shared + (int64_t)wpb * a.wave_floats);
-  const int64_t per_cu = std::max<int64_t>(1, (160 * 1024) / (int64_t)lds);
+  pick.a.bits = bits;
+  pick.a.y = y;
+  const int wpb = pick.v->wpb;
+  const int64_t per_cu = std::max<int64_t>(1, (160 * 1024) / (int64_t)pick.lds);
   const int64_t grid = std::min<int64_t>(cdiv(rows, wpb), 256 * per_cu);
-#define XPG_FUSED(W)                                                                                     \
-  if (wpb == W) {                                                                                        \
-    XPG_HIP(lds_limit(reinterpret_cast<const void*>(&k_fused_forward<W>)));       \
-    hipLaunchKernelGGL(k_fused_forward<W>, dim3(static_cast<unsigned>(grid)), dim3(W * 64), lds, st, a); \
-    XPG_LAUNCHED();                                                                                      \
-    return XPG_OK;                                                                                       \
-  }
-  XPG_FUSED(8) XPG_FUSED(4) XPG_FUSED(2)
-#undef XPG_FUSED
-  return 1;
+  XPG_HIP(lds_limit(reinterpret_cast<const void*>(pick.v->fn)));
+  hipLaunchKernelGGL(pick.v->fn, dim3(static_cast<unsigned>(grid)), dim3(wpb * 64), pick.lds, st, pick.a);
+  XPG_LAUNCHED();
+  return XPG_OK;
 }
 
 int device_cus() {
@@ -8556,10 +8634,26 @@ int run_wide_forward(const xpg_forward_plan* p, const WideWs& W, const uint32_t*
   return XPG_OK;
 }
 
-// Lanes-=-rows fused forward for 1- and 2-layer plans (returns 1 when it does not apply).  `dry`:
-// the decision only (XPG_OK = the kernel takes the plan), nothing launched, no device touched.
-int try_rows_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t rows, float* y, hipStream_t st,
-                     int* ctl, bool dry = false) {
+struct RowsVariant {
+  void (*fn)(const RowsFwdArgs);
+  const char* name;
+  int fs;
+  bool sumk;
+};
+#define XPG_RV(F) {k_rows_forward<F, false>, "k_rows_forward<" #F ",0>", F, false}, {k_rows_forward<F, true>, "k_rows_forward<" #F ",1>", F, true}
+const RowsVariant kRowsVariants[] = {XPG_RV(2), XPG_RV(4), XPG_RV(8)};
+#undef XPG_RV
+struct RowsPick {
+  const RowsVariant* v;
+  size_t lds;
+  RowsFwdArgs a;  // everything but bits, y, ctl and the device's block schedule; its run-time forms:
+                  // a.stage_bits, a.w2_lds, a.o_hw[i] >= 0 (mask rows / layer-2 weights / head layer i in LDS)
+};
+
+// The rows kernel's variant, LDS layout (with its run-time forms) and arguments when the plan fits
+// (returns 1 when it does not apply): plan fields only, no device touched.
+int rows_pick(const xpg_forward_plan* p, int64_t rows, RowsPick* s) {
+  RowsFwdArgs& a = s->a;
   if (p->n_layers < 1 || p->n_layers > 2 || p->n_head > kFusedMaxHead || plan_multi_type(p)) return 1;
   if (p->edge_masks || p->edge_dot) return 1;  // edge problems: multi-kernel path only
   if (plan_has_attention(p)) return 1;         // attention: multi-kernel path only
@@ -8567,11 +8661,8 @@ int try_rows_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t ro
   if (plan_pool(p)) return 1;                  // pooled plans (readout): multi-kernel path only
   // SUM runs here (MEAN with inv = 1); MAX fits no per-edge coefficient and a raw layer 1 has no tables
   if (plan_has_kind(p, XPG_TERM_MAX) || plan_raw_l1(p)) return 1;
-  RowsFwdArgs a;
   std::memset(&a, 0, sizeof(a));
   a.rows = rows;
-  a.bits = bits;
-  a.y = y;
   a.words = words_of(p->cols);
   a.n0 = p->n0;
   a.n_rel = p->n_rel;
@@ -8687,8 +8778,24 @@ int try_rows_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t ro
     const int64_t n = (int64_t)p->head[i].n_pad * p->head[i].k_pad;
     if (off + n <= cap) a.o_hw[i] = take(n);
   }
-  const size_t lds = sizeof(float) * (size_t)off;
+  s->lds = sizeof(float) * (size_t)off;
+  const bool sumk = plan_has_kind(p, XPG_TERM_SUM);  // SUM terms: the instantiation that knows them
+  s->v = nullptr;
+  for (const RowsVariant& v : kRowsVariants)
+    if (v.fs == fs && v.sumk == sumk) s->v = &v;
+  return s->v ? XPG_OK : 1;
+}
+
+// Lanes-=-rows fused forward for 1- and 2-layer plans (returns 1 when it does not apply).  `dry`:
+// the decision only (XPG_OK = the kernel takes the plan), nothing launched, no device touched.
+int try_rows_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t rows, float* y, hipStream_t st,
+                     int* ctl, bool dry = false) {
+  RowsPick pick;
+  if (const int rc = rows_pick(p, rows, &pick)) return rc;
   if (dry) return XPG_OK;
+  RowsFwdArgs& a = pick.a;
+  a.bits = bits;
+  a.y = y;
   a.n_blocks = static_cast<int>(cdiv(rows, 64));
   a.cus_per_xcd = std::max(1, device_cus() / device_xcds());
   a.ctl = ctl;
@@ -8699,22 +8806,10 @@ int try_rows_forward(const xpg_forward_plan* p, const uint32_t* bits, int64_t ro
                                                   (int64_t)a.n_blocks + 4 * a.cus_per_xcd));
   }
   const dim3 grid(nwg);
-  const bool sumk = plan_has_kind(p, XPG_TERM_SUM);  // SUM terms: the instantiation that knows them
-#define XPG_ROWS(F)                                                                                     \
-  if (fs == F) {                                                                                        \
-    if (sumk) {                                                                                         \
-      XPG_HIP(lds_limit(reinterpret_cast<const void*>(&k_rows_forward<F, true>)));                       \
-      hipLaunchKernelGGL((k_rows_forward<F, true>), grid, dim3(64 * kRowsWaves), lds, st, a);             \
-    } else {                                                                                            \
-      XPG_HIP(lds_limit(reinterpret_cast<const void*>(&k_rows_forward<F>)));                             \
-      hipLaunchKernelGGL(k_rows_forward<F>, grid, dim3(64 * kRowsWaves), lds, st, a);                    \
-    }                                                                                                   \
-    XPG_LAUNCHED();                                                                                     \
-    return XPG_OK;                                                                                      \
-  }
-  XPG_ROWS(2) XPG_ROWS(4) XPG_ROWS(8)
-#undef XPG_ROWS
-  return 1;
+  XPG_HIP(lds_limit(reinterpret_cast<const void*>(pick.v->fn)));
+  hipLaunchKernelGGL(pick.v->fn, grid, dim3(64 * kRowsWaves), pick.lds, st, a);
+  XPG_LAUNCHED();
+  return XPG_OK;
 }
 
 // The path xpg_masked_forward takes for a plan under the current environment (host only; the one
@@ -8855,6 +8950,73 @@ int comm_pick(int64_t rows, int64_t cols, int32_t n_comm, int32_t n_blocks, Comm
     p->name = staged ? "k_communities<0,1,0>" : "k_communities<0,0,0>";
   }
   return XPG_OK;
+}
+
+// The multi-kernel path's tail (host only; the one decision behind the launches and behind
+// xpg_forward_kernels).  The picked output column is fused into the last dense layer's epilogue
+// (k_dense HEAD) when the network ends in a head layer that follows a dense layer (another head
+// layer, or a conv layer past the first) and no link decoder: no 32-wide padded head tile, no
+// column pick.  Otherwise k_take_col picks the column (or the link decoder / class readout runs).
+struct TailPick {
+  bool fuse_out;  // the last head layer runs in a k_dense HEAD epilogue
+  int conv;       // ... of this conv layer's dense launch (0-based), or -1
+  int head;       // ... of this head layer's dense launch (0-based), or -1
+};
+TailPick tail_pick(const xpg_forward_plan* p, const xpg_post_desc* post, const xpg_class_out* cls) {
+  TailPick t{false, -1, -1};
+  // A pooled plan's head follows the readout, which is no dense layer: its last head layer is
+  // fused only into the head layer before it (k_dense HEAD on M = rows rows, as for one query).
+  // Nor does an ATT2 or QKV last layer end in a dense launch (its kernel finishes the layer itself).
+  const int pool = plan_pool(p);
+  const bool last_att2 =
+      layer_has_att2(p->layers[p->n_layers - 1]) || layer_has_qkv(p->layers[p->n_layers - 1]);
+  // Nor may a last conv layer with a post-op take the column pick or the first head layer into its
+  // k_dense epilogue: the post-op runs between the two.
+  const bool last_post = plan_has_post(p, post) && post_any(post[p->n_layers - 1]);
+  // Nor does a class readout fuse: the HEAD epilogue keeps one column, softmax needs them all.
+  if (!cls && !p->edge_dot && p->n_head >= 1 &&
+      (p->n_head >= 2 || (p->n_layers >= 2 && !pool && !last_att2 && !last_post))) {
+    const xpg_head_desc& hl = p->head[p->n_head - 1];
+    const int64_t prev_pad = p->n_head >= 2 ? p->head[p->n_head - 2].n_pad : p->layers[p->n_layers - 1].f_out_pad;
+    if (hl.k_pad == prev_pad && p->out_col >= 0 && p->out_col < hl.n_real) {
+      t.fuse_out = true;
+      if (p->n_head == 1) t.conv = p->n_layers - 1;
+      else t.head = p->n_head - 2;
+    }
+  }
+  return t;
+}
+
+// One conv layer of the multi-kernel path (host only; the one decision behind run_layer's launches
+// and behind xpg_forward_kernels): which kernel family aggregates, the row width it is handed,
+// and the dense launch that follows, if any.
+struct LayerPick {
+  enum Family { kPlain, kAtt, kAtt2, kQkv, kRel } family;
+  bool raw;       // layer 1 in its raw form: aggregate X[F_0], then the dense product
+  bool table_l1;  // layer 1 in its table form: the aggregation kernel finishes the layer
+  int agg_width;  // kPlain: the row width of the aggregation kernel
+  bool dense;     // a dense launch follows the aggregation
+  int64_t K;      // ... with this k_pad (= lda = ldw)
+  bool head;      // ... and the output column in its epilogue (tail_pick)
+};
+LayerPick layer_pick(const xpg_forward_plan* p, int l, const TailPick& tail) {
+  const xpg_layer_desc& ly = p->layers[l];
+  LayerPick s;
+  s.family = layer_has_att2(ly)        ? LayerPick::kAtt2
+             : layer_has_qkv(ly)       ? LayerPick::kQkv
+             : layer_has_attention(ly) ? LayerPick::kAtt
+             : layer_has_rel(ly)       ? LayerPick::kRel
+                                       : LayerPick::kPlain;
+  s.raw = l == 0 && plan_raw_l1(p);
+  s.table_l1 = l == 0 && !s.raw;
+  s.agg_width = s.table_l1 ? ly.f_out_pad : ly.f_in_pad;
+  // ATT2 / QKV kernels finish their layer themselves; layer 1 of the others is complete after its
+  // aggregation unless it takes the raw form (plain layers only)
+  s.dense = s.family != LayerPick::kAtt2 && s.family != LayerPick::kQkv &&
+            (l > 0 || (s.raw && s.family == LayerPick::kPlain));
+  s.K = (int64_t)layer_slices(ly) * ly.f_in_pad;
+  s.head = s.dense && tail.conv == l;
+  return s;
 }
 
 }  // namespace
@@ -9292,6 +9454,127 @@ int xpg_wide_variants(char* buf, size_t n) {
   return XPG_OK;
 }
 
+int xpg_forward_variants(char* buf, size_t n) {
+  XPG_REQ(buf != nullptr && n > 0, "forward_variants: no buffer");
+  buf[0] = 0;
+  std::string s;
+  for (const RowsVariant& v : kRowsVariants) s += std::string(v.name) + "\n";
+  for (const FusedVariant& v : kFusedVariants) s += std::string(v.name) + "\n";
+  for (const AggVariant& v : kAggVariants) s += std::string(v.name) + "\n";
+  for (const DenseVariant& v : kDenseVariants) s += std::string(v.name) + "\n";
+  if (s.size() + 1 > n) return fail(XPG_ENOSPC, "forward_variants: buffer too small");
+  std::memcpy(buf, s.c_str(), s.size() + 1);
+  return XPG_OK;
+}
+
+int xpg_forward_kernels(const xpg_forward_plan* p, int64_t rows, char* buf, size_t n) {
+  return xpg_forward_kernels_c(p, nullptr, nullptr, nullptr, nullptr, rows, buf, n);
+}
+
+int xpg_forward_kernels_c(const xpg_forward_plan* p, const xpg_post_desc* post, const xpg_edge_weights* wts,
+                          const xpg_edge_feats* feats, const xpg_class_out* cls, int64_t rows, char* buf,
+                          size_t n) {
+  XPG_REQ(buf != nullptr && n > 0, "forward_kernels: no buffer");
+  buf[0] = 0;
+  int rc = weights_plan_check(p, wts);
+  if (rc) return rc;
+  rc = feats_plan_check(p, wts, feats);
+  if (rc) return rc;
+  WsLayout L;
+  rc = layout_ws(p, rows, &L, wts);
+  if (rc) return rc;
+  XPG_REQ(p->n_rel >= 1 && p->n0 >= 1 && p->cols > 0, "masked_forward: bad plan sizes");
+  rc = post_plan_check(p, post);
+  if (rc) return rc;
+  rc = class_plan_check(p, post, cls);
+  if (rc) return rc;
+  const bool has_post = plan_has_post(p, post);
+  WideWs W;
+  FwdPath path;
+  rc = forward_route(p, rows, &W, &path, nullptr, has_post || wts != nullptr || feats != nullptr || cls != nullptr);
+  if (rc) return rc;
+  if (path == kPathNone) return fail(XPG_EINVAL, kStrictMsg);
+  std::string s = kPathName[path];
+  if (path == kPathWide) {
+    WidePick pick;
+    rc = wide_select(p, W, &pick);
+    if (rc) return rc;
+    s += std::string(" l1=") + pick.k1->name + " l2=" + pick.k2->name;
+  } else if (path == kPathRows) {
+    RowsPick pick;
+    rc = rows_pick(p, rows, &pick);
+    if (rc) return rc == 1 ? fail(XPG_EINVAL, "forward_kernels: the rows kernel does not take this plan") : rc;
+    s += std::string(" ") + pick.v->name + " layers=" + std::to_string(p->n_layers) +
+         " bits=" + (pick.a.stage_bits ? "lds" : "global") +
+         " w2=" + (p->n_layers < 2 ? "-" : pick.a.w2_lds ? "lds" : "global") + " head=";
+    for (int i = 0; i < p->n_head; ++i) s += std::string(i ? "," : "") + (pick.a.o_hw[i] >= 0 ? "lds" : "global");
+    if (!p->n_head) s += "-";
+  } else if (path == kPathFused) {
+    FusedPick pick;
+    rc = fused_pick(p, rows, &pick);
+    if (rc) return rc == 1 ? fail(XPG_EINVAL, "forward_kernels: the fused kernel does not take this plan") : rc;
+    s += std::string(" ") + pick.v->name + " layers=" + std::to_string(p->n_layers) + " tpp=";
+    for (int l = 1; l < p->n_layers; ++l)  // targets per pass of each layer past the first
+      s += std::string(l > 1 ? "," : "") + std::to_string(64 / (p->layers[l].f_in_pad / 4));
+    if (p->n_layers < 2) s += "-";
+  } else {
+    // the multi-kernel path: per conv layer its aggregation kernel (by family where the family has
+    // its own query or file: weighted, edge-featured, attention, relation layers) and dense launch,
+    // then the head layers' dense launches and the tail
+    const TailPick tail = tail_pick(p, post, cls);
+    auto dense = [&](int64_t k_pad, int64_t n_pad, bool head, bool typed, std::string* out) -> int {
+      DensePick d;
+      if (const int r = dense_pick(k_pad, n_pad, head, &d)) return r;
+      *out += std::string(d.v->name) + "g" + std::to_string(d.groups) + (typed ? "t" : "");
+      return XPG_OK;
+    };
+    for (int l = 0; l < p->n_layers; ++l) {
+      const xpg_layer_desc& ly = p->layers[l];
+      const LayerPick lp = layer_pick(p, l, tail);  // run_layer's own record
+      XPG_REQ(!lp.raw || (ly.f_in_pad % 32 == 0 && ly.f_in_pad <= 256),
+              "raw layer 1: f_in_pad must be 32..256, a multiple of 32");
+      s += " l" + std::to_string(l + 1) + "=";
+      // attention and relation layers: the family only (their kernels have their own files)
+      if (lp.family == LayerPick::kAtt2) s += "att2";
+      else if (lp.family == LayerPick::kQkv) s += "qkv";
+      else if (lp.family == LayerPick::kAtt) s += "att";
+      else if (lp.family == LayerPick::kRel) s += "rel";
+      else if (feats) s += "k_agg_e";
+      else if (wts) s += "k_agg_w";
+      else {
+        int kind[XPG_MAX_TERMS];
+        XPG_REQ(ly.n_terms >= 1 && ly.n_terms <= XPG_MAX_TERMS, "layer: 1..8 terms");
+        for (int k = 0; k < ly.n_terms; ++k) kind[k] = ly.terms[k].kind;
+        AggPick a;
+        rc = agg_pick(lp.table_l1, p->edge_masks != 0, lp.agg_width, kind, ly.n_terms, &a);
+        if (rc) return rc;
+        s += a.v->name;
+        if (a.v->rows) s += "x" + std::to_string(a.slices);
+      }
+      if (lp.dense) {
+        s += "+";
+        rc = dense(lp.K, ly.f_out_pad, lp.head, ly.tgt_type != nullptr, &s);
+        if (rc) return rc;
+      }
+    }
+    s += " head=";
+    const int n_head_launch = p->n_head - (tail.fuse_out ? 1 : 0);
+    for (int i = 0; i < n_head_launch; ++i) {
+      if (i) s += ",";
+      rc = dense(p->head[i].k_pad, p->head[i].n_pad, tail.head == i, false, &s);
+      if (rc) return rc;
+    }
+    if (!n_head_launch) s += "-";
+    s += std::string(" tail=") + (tail.fuse_out ? "epilogue"
+                                  : p->edge_dot ? (p->dot_scale ? "k_edge_dot_scaled" : "k_edge_dot")
+                                  : cls         ? class_kernel_name(cls->kind, cls->col < 0)
+                                                : "k_take_col");
+  }
+  if (s.size() + 1 > n) return fail(XPG_ENOSPC, "forward_kernels: buffer too small");
+  std::memcpy(buf, s.c_str(), s.size() + 1);
+  return XPG_OK;
+}
+
 int xpg_pool_workspace(int64_t rows, int64_t n, int64_t ld, size_t* bytes) {
   XPG_REQ(bytes != nullptr, "pool_workspace: no output");
   PoolPick pick;
@@ -9408,32 +9691,16 @@ int xpg_masked_forward_c(const xpg_forward_plan* p, const xpg_post_desc* post, c
   float* kin = reinterpret_cast<float*>(ws + L.kin);
   const int words = words_of(p->cols);
   const int kpitch = deg_pitch(p);
-  // The picked output column is fused into the last dense layer's epilogue (k_dense HEAD) when the
-  // network ends in a head layer that follows a dense layer (another head layer, or a conv layer
-  // past the first) and no link decoder: no 32-wide padded head tile, no column pick.
-  OutColumn fh;
-  bool fuse_out = false;
-  // A pooled plan's head follows the readout, which is no dense layer: its last head layer is
-  // fused only into the head layer before it (k_dense HEAD on M = rows rows, as for one query).
-  // Nor does an ATT2 or QKV last layer end in a dense launch (its kernel finishes the layer itself).
   const int pool = plan_pool(p);
-  const bool last_att2 =
-      layer_has_att2(p->layers[p->n_layers - 1]) || layer_has_qkv(p->layers[p->n_layers - 1]);
-  // Nor may a last conv layer with a post-op take the column pick or the first head layer into its
-  // k_dense epilogue: the post-op runs between the two.
-  const bool last_post = has_post && post_any(post[p->n_layers - 1]);
-  // Nor does a class readout fuse: the HEAD epilogue keeps one column, softmax needs them all.
-  if (!cls && !p->edge_dot && p->n_head >= 1 &&
-      (p->n_head >= 2 || (p->n_layers >= 2 && !pool && !last_att2 && !last_post))) {
+  OutColumn fh;
+  const TailPick tail = tail_pick(p, post, cls);
+  const bool fuse_out = tail.fuse_out;
+  if (fuse_out) {
     const xpg_head_desc& hl = p->head[p->n_head - 1];
-    const int64_t prev_pad = p->n_head >= 2 ? p->head[p->n_head - 2].n_pad : p->layers[p->n_layers - 1].f_out_pad;
-    if (hl.k_pad == prev_pad && p->out_col >= 0 && p->out_col < hl.n_real) {
-      fuse_out = true;
-      fh.w = hl.weight + (int64_t)p->out_col * hl.k_pad;
-      fh.b = hl.bias + p->out_col;
-      fh.act = hl.act;
-      fh.y = y;
-    }
+    fh.w = hl.weight + (int64_t)p->out_col * hl.k_pad;
+    fh.b = hl.bias + p->out_col;
+    fh.act = hl.act;
+    fh.y = y;
   }
   if (plan_needs_degree(p)) {
     const int64_t n = rows * (int64_t)p->n_rel * kpitch;
@@ -9486,7 +9753,8 @@ int xpg_masked_forward_c(const xpg_forward_plan* p, const xpg_post_desc* post, c
   auto run_layer = [&](int l) -> int {
     const xpg_layer_desc& ly = p->layers[l];
     XPG_REQ(ly.n_terms >= 1 && ly.n_terms <= XPG_MAX_TERMS, "layer: 1..8 terms");
-    const bool raw = l == 0 && plan_raw_l1(p);
+    const LayerPick lp = layer_pick(p, l, tail);
+    const bool raw = lp.raw;
     if (layer_has_att2(ly)) {
       rc = launch_att2_layer(p, l, bits, rows, l == 0 ? nullptr : reinterpret_cast<const float*>(ws + L.h[l - 1]),
                              reinterpret_cast<float*>(ws + L.xlr), reinterpret_cast<float*>(ws + L.h[l]), st);
@@ -9513,8 +9781,8 @@ int xpg_masked_forward_c(const xpg_forward_plan* p, const xpg_post_desc* post, c
       rc = launch_att_layer(p, l, bits, rows, reinterpret_cast<const float*>(ws + L.h[l - 1]),
                             reinterpret_cast<float*>(ws + L.score), agg, st);
       if (rc) return rc;
-      const int64_t K = (int64_t)layer_slices(ly) * ly.f_in_pad;
-      const bool fuse_here = fuse_out && p->n_head == 1 && l == p->n_layers - 1;
+      const int64_t K = lp.K;
+      const bool fuse_here = lp.head;
       rc = launch_dense(agg, rows * ly.n_tgt, K, ly.weight, K, K, ly.bias, ly.f_out, ly.f_out_pad, ly.act, hout,
                         ly.f_out_pad, st, ly.tgt_type, ly.n_tgt, ly.f_out_pad, fuse_here ? &fh : nullptr);
       if (rc) return rc;
@@ -9532,8 +9800,8 @@ int xpg_masked_forward_c(const xpg_forward_plan* p, const xpg_post_desc* post, c
       float* agg = reinterpret_cast<float*>(ws + L.agg);
       rc = launch_rel_layer(p, l, bits, rows, reinterpret_cast<const float*>(ws + L.h[l - 1]), agg, st);
       if (rc) return rc;
-      const int64_t K = (int64_t)layer_slices(ly) * ly.f_in_pad;
-      const bool fuse_here = fuse_out && p->n_head == 1 && l == p->n_layers - 1;
+      const int64_t K = lp.K;
+      const bool fuse_here = lp.head;
       rc = launch_dense(agg, rows * ly.n_tgt, K, ly.weight, K, K, ly.bias, ly.f_out, ly.f_out_pad, ly.act, hout,
                         ly.f_out_pad, st, ly.tgt_type, ly.n_tgt, ly.f_out_pad, fuse_here ? &fh : nullptr);
       if (rc) return rc;
@@ -9592,16 +9860,16 @@ int xpg_masked_forward_c(const xpg_forward_plan* p, const xpg_post_desc* post, c
       a.hstride = 0;
       a.tgt_prev = ly.tgt_f0;
       a.agg_src = ly.agg_f0;
-      a.width = ly.f_in_pad;
+      a.width = lp.agg_width;
       a.out = agg;
-      a.out_ld = (int64_t)ly.n_terms * ly.f_in_pad;
+      a.out_ld = lp.K;
       rc = agg_launch(a, false, l);
       if (rc) return rc;
       rc = launch_dense(agg, rows * ly.n_tgt, a.out_ld, ly.weight, a.out_ld, a.out_ld, ly.bias, ly.f_out,
                         ly.f_out_pad, ly.act, hout, ly.f_out_pad, st, ly.tgt_type, ly.n_tgt, ly.f_out_pad, nullptr);
       if (rc) return rc;
-    } else if (l == 0) {
-      a.width = ly.f_out_pad;
+    } else if (lp.table_l1) {
+      a.width = lp.agg_width;
       a.out = hout;
       a.out_ld = ly.f_out_pad;
       a.bias = ly.bias;
@@ -9615,12 +9883,12 @@ int xpg_masked_forward_c(const xpg_forward_plan* p, const xpg_post_desc* post, c
       float* agg = reinterpret_cast<float*>(ws + L.agg);
       a.hprev = reinterpret_cast<const float*>(ws + L.h[l - 1]);
       a.hstride = (int64_t)a.n_prev * ly.f_in_pad;
-      a.width = ly.f_in_pad;
+      a.width = lp.agg_width;
       a.out = agg;
-      a.out_ld = (int64_t)ly.n_terms * ly.f_in_pad;
+      a.out_ld = lp.K;
       rc = agg_launch(a, false, l);
       if (rc) return rc;
-      const bool fuse_here = fuse_out && p->n_head == 1 && l == p->n_layers - 1;
+      const bool fuse_here = lp.head;
       rc = launch_dense(agg, rows * ly.n_tgt, a.out_ld, ly.weight, a.out_ld, a.out_ld, ly.bias, ly.f_out,
                         ly.f_out_pad, ly.act, hout, ly.f_out_pad, st, ly.tgt_type, ly.n_tgt, ly.f_out_pad,
                         fuse_here ? &fh : nullptr);
@@ -9658,7 +9926,7 @@ int xpg_masked_forward_c(const xpg_forward_plan* p, const xpg_post_desc* post, c
     XPG_REQ(hd.k_pad == cur_ld, "head: k_pad must equal the previous padded width");
     float* nxt = reinterpret_cast<float*>(ws + ((i & 1) ? L.head1 : L.head0));
     rc = launch_dense(cur, M, cur_ld, hd.weight, hd.k_pad, hd.k_pad, hd.bias, hd.n_real, hd.n_pad, hd.act, nxt,
-                      hd.n_pad, st, nullptr, 1, 0, fuse_out && i == n_head_launch - 1 ? &fh : nullptr);
+                      hd.n_pad, st, nullptr, 1, 0, tail.head == i ? &fh : nullptr);
     if (rc) return rc;
     cur = nxt;
     cur_ld = hd.n_pad;

@@ -512,6 +512,15 @@ def wide_variants():
     return buf.value.decode().split()
 
 
+def forward_variants():
+    """Every instantiation of k_rows_forward, k_fused_forward, k_agg_l1_rows, k_agg and k_dense in
+    the library (xpg_forward_variants: the tables the launches pick from), by the names
+    ForwardPlan.kernels reports."""
+    buf = ctypes.create_string_buffer(4096)
+    _lib.check(_lib.load().xpg_forward_variants(buf, len(buf)))
+    return buf.value.decode().split()
+
+
 # ----------------------------------------------------------------------------- readout
 def pool_describe(rows: int, n: int, ld: int, kind: str) -> str:
     """The kernel(s) the readout launches for h [rows, n, ld] (xpg_pool_describe, a host query
@@ -1634,6 +1643,25 @@ class ForwardPlan:
         buf = ctypes.create_string_buffer(1024)
         name, lead = self._entry("xpg_forward_describe")
         _lib.check(getattr(_lib.load(), name)(*lead, rows, buf, len(buf)))
+        return buf.value.decode()
+
+    def kernels(self, rows):
+        """What forward() launches for `rows` mask rows under the current environment, by
+        instantiation and run-time form (xpg_forward_kernels, a host query of the picks the launches
+        use), e.g. "rows k_rows_forward<4,0> layers=2 bits=lds w2=global head=lds,global",
+        "fused k_fused_forward<4> layers=3 tpp=8,4" or "unfused l1=k_agg_l1_rows<64,1>x2
+        l2=k_agg<0,24,1>+k_dense<3,0>g1 head=k_dense<1,1>g1 tail=epilogue"; the wide path reads as
+        in describe().  Raises where forward() would refuse the plan."""
+        buf = ctypes.create_string_buffer(1024)
+        lib = _lib.load()
+        if self._post is None and self._weights is None and self._feats is None and self._cls is None:
+            _lib.check(lib.xpg_forward_kernels(ctypes.byref(self.desc), rows, buf, len(buf)))
+        else:
+            _lib.check(lib.xpg_forward_kernels_c(
+                ctypes.byref(self.desc), self._post,
+                ctypes.byref(self._weights) if self._weights is not None else None,
+                ctypes.byref(self._feats) if self._feats is not None else None,
+                ctypes.byref(self._cls) if self._cls is not None else None, rows, buf, len(buf)))
         return buf.value.decode()
 
     def forward(self, bits: torch.Tensor, max_ws_bytes=8 << 30, out: torch.Tensor = None,

@@ -50,6 +50,8 @@
  *                                        global_add_pool / global_max_pool over one graph per row)
  *   xpg_forward_describe / xpg_wide_variants — none: host queries of xpg_masked_forward's own
  *                                        dispatch (path and wide-path kernels), for tests and logs
+ *   xpg_forward_kernels / xpg_forward_variants — none: the same for the rows, fused and multi-kernel
+ *                                        paths (instantiation and run-time form of every launch)
  *   xpg_sampler_describe               — none: host query of the device samplers' own dispatch (which
  *                                        k_shapley / k_shapley_flat / k_communities instantiation
  *                                        a shape launches, and its grid), for tests and logs
@@ -719,6 +721,36 @@ int xpg_forward_describe_c(const xpg_forward_plan* plan, const xpg_post_desc* po
  * 1 <= n_real <= ld) -> out [M] (col >= 0) or [M][n_real] (col == -1). */
 int xpg_class_out_rows(const float* in, int64_t M, int64_t ld, int64_t n_real, int32_t kind,
                        int32_t col, float* out, xpg_stream_t stream);
+
+/* The kernels behind xpg_forward_describe's `rows`, `fused` and `unfused` (v28 addendum: new symbols
+ * only; the version, every struct above and every entry point above are unchanged).  HOST functions:
+ * they launch nothing and touch no device; the launches dispatch on the same pick records
+ * (rows_pick, fused_pick, layer_pick, agg_pick, dense_pick, tail_pick) these texts are printed from.
+ * xpg_forward_kernels writes what xpg_masked_forward would launch for the plan, row count and
+ * environment, one of
+ *   `rows k_rows_forward<4,0> layers=2 bits=lds w2=global head=lds,global`
+ *        k_rows_forward<FS, SUMK> (FS = f1_pad / 16 features per wave, SUMK = a SUM term) and its
+ *        run-time forms: mask rows staged in LDS or read from global memory, layer 2's weights
+ *        (`-`: one layer), each head layer's weights (`-`: no head layer)
+ *   `fused k_fused_forward<4> layers=3 tpp=8,4`
+ *        k_fused_forward<waves per block>; targets per pass of each layer past the first
+ *   `unfused l1=k_agg_l1_rows<64,1>x2 l2=k_agg<0,24,1>+k_dense<3,0>g1 head=k_dense<1,1>g1 tail=epilogue`
+ *        per conv layer its aggregation kernel, k_agg_l1_rows<features per wave, ONE> x feature
+ *        slices or k_agg<L1, LPS, NV>, `+` its dense launch k_dense<NT, HEAD> g column groups (`t`:
+ *        per-type bias rows); then the head layers' dense launches (`-`: none) and the tail:
+ *        `epilogue` (the output column computed in the k_dense<NT,1> launch named before it),
+ *        `k_take_col`, `k_edge_dot`, `k_edge_dot_scaled` or the class readout's kernel.  Weighted
+ *        and edge-featured layers read `k_agg_w` / `k_agg_e`, attention and relation layers
+ *        `att` / `att2` / `qkv` / `rel` (their own tests name those kernels), followed by `+` and
+ *        the layer's dense launch where it has one (`att` / `rel` layers past the first).
+ *   `wide l1=... l2=...`  as xpg_forward_describe.
+ * Fails where xpg_forward_describe fails.  xpg_forward_variants lists every instantiation of
+ * k_rows_forward, k_fused_forward, k_agg_l1_rows, k_agg and k_dense in the library, one per line. */
+int xpg_forward_kernels(const xpg_forward_plan* plan, int64_t rows, char* buf, size_t n);
+int xpg_forward_kernels_c(const xpg_forward_plan* plan, const xpg_post_desc* post,
+                          const xpg_edge_weights* weights, const xpg_edge_feats* feats,
+                          const xpg_class_out* cls, int64_t rows, char* buf, size_t n);
+int xpg_forward_variants(char* buf, size_t n);
 
 /* Optional per-kernel timing of xpg_masked_forward's wide (full-graph) path (v13): with profiling
  * on, every launch of a profiled kernel is bracketed by two hipEvents on its stream;
